@@ -24,9 +24,28 @@ keys are orderkey-led, so rows group-colocate after the orderkey shuffle
 and the local aggregate is final (the reference optimizer's own colocation
 reasoning).
 
-CPU baseline (rank 0, N=1 only): the C++ oracle ("port") on ALL host
-cores, one thread per core (BASELINE.md protocol), bounded sample, core
-count stated in the JSON.
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps steps, print the result line. Everything else sits behind
+--full:
+
+CPU baseline (--full; rank 0, N=1 only): the C++ oracle ("port") on ALL
+host cores, one thread per core (BASELINE.md protocol), bounded sample,
+core count stated in the JSON ("cpu_baseline" is null without --full).
+
+--dump-outputs DIR writes what the LAST timed step computed as
+DIR/<name>.npy (float64; rank r>0 writes <name>.rank<r>.npy). Inputs are
+seeded, so two builds run with the same arguments can be compared output
+for output. Row sets come back in no defined order, so they are written
+sorted by key; one larger than DUMP_MAX_ROWS is cut to a fixed sample
+chosen by a hash of each row's key (independent of row order).
+  counts.npy        every workload: the step's cardinalities, in the order
+                    of that workload's COUNT_KEYS
+  groups.npy        c3: (rows, 6) l_orderkey, o_orderdate, o_shippriority,
+                    SUM(revenue) f64, SUM(rev_scaled4), COUNT(*)
+                    c5: (rows, 4) nationkey, o_year, SUM(amount4), COUNT(*)
+  group_totals.npy  c3: n_groups and the three aggregate columns summed
+                    over ALL groups (not only the sampled ones)
+  join_rows.npy     c2: (rows, 4) l_orderkey, l_pay, o_orderkey, o_pay
 """
 import argparse
 import json
@@ -39,6 +58,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 
 HBM_PEAK_BYTES_PER_S = 8.0e12  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_MAX_ROWS = 1_000_000      # x <= 6 float64 columns = 48 MB (cap: 64 MB)
 
 
 def next_pow2(x):
@@ -75,6 +95,33 @@ def probe_bytes_per_row(n_build, matches, probe_rows):
     m = matches / probe_rows if probe_rows else 0.0
     s = max(1.0, m + n_build / n_buckets)
     return 4 + 1 + 8 + 16 * s + 8 * m
+
+
+def canonical_rows(cols, key_cols, max_rows=DUMP_MAX_ROWS):
+    """--dump-outputs: canonical float64 (rows, len(cols)) image of a row
+    set held as equal-length torch columns. Rows are sorted by the integer
+    key_cols (which must identify a row up to duplicates); above max_rows a
+    fixed subset is kept, chosen by a multiplicative hash of the key so the
+    choice does not depend on the order the operator emitted the rows in."""
+    import torch
+    n = cols[0].numel() if cols else 0
+    if n > max_rows:
+        h = torch.zeros(n, dtype=torch.int64, device=cols[0].device)
+        for k in key_cols:
+            h = (h ^ cols[k].to(torch.int64)) * 0x9E3779B1  # wraps mod 2^64
+        h = (h ^ (h >> 31)) * 0x9E3779B1
+        h = (h >> 24) & 0xFFFFF
+        pick = h < int((1 << 20) * 0.9 * max_rows / n)
+        cols = [c[pick] for c in cols]
+    host = [c.cpu().numpy() for c in cols]
+    if not host:
+        return np.zeros((0, 0))
+    order = np.lexsort([host[k] for k in reversed(key_cols)])[:max_rows]
+    return np.stack([a[order].astype(np.float64) for a in host], axis=1)
+
+
+def counts_array(info, keys):
+    return np.array([float(info.get(k) or 0) for k in keys])
 
 
 def load_traffic(workload):
@@ -117,7 +164,9 @@ class C2:
         self.n_probe = lkeys.numel()
         self.n_build = okeys.numel()
 
-    def step(self, lib, local_rank, distributed):
+    COUNT_KEYS = ("n_out",)
+
+    def step(self, lib, local_rank, distributed, keep=None):
         import ctypes as C
         from galaxysql_amd import abi
         from galaxysql_amd.abi import GxResult
@@ -143,7 +192,11 @@ class C2:
                       "probe")
             n_out = out.contents.chunk.n_rows if out else 0
             if out:
-                lib.lib.gxop_result_release(out)
+                if keep is not None:
+                    keep.append(out)  # --dump-outputs: main() releases
+                else:
+                    lib.lib.gxop_result_release(out)
+            self.last_info = {"n_out": n_out}
             st = op.stats()
             st["n_build"] = b[0].numel()
             st["groups"] = 0
@@ -161,6 +214,15 @@ class C2:
                 "output": "full 4-column materialization",
                 "exchange": "rccl_all_to_allv" if world > 1 else "none",
                 "parallelism": f"hash_shuffle_dp{world}"}
+
+    def outputs(self, lib, device, kept):
+        from galaxysql_amd.chunk import I64
+        from galaxysql_amd.queries import result_to_tensors
+        out = {"counts": counts_array(self.last_info, self.COUNT_KEYS)}
+        if kept:
+            cols = result_to_tensors(lib, kept[0], [I64] * 4, device)
+            out["join_rows"] = canonical_rows(cols, [0, 1, 2, 3])
+        return out
 
     def cpu_baseline(self, sample_rows, threads=1):
         return c2_cpu_baseline(self.n_build, sample_rows, threads=threads)
@@ -188,7 +250,7 @@ class C2Chunk(C2):
         self.chunk_size = args.chunk_size
         self.flush_rows = args.flush_rows
 
-    def step(self, lib, local_rank, distributed):
+    def step(self, lib, local_rank, distributed, keep=None):
         import ctypes as C
         from galaxysql_amd import abi
         from galaxysql_amd.abi import GxResult
@@ -246,6 +308,7 @@ class C2Chunk(C2):
             st["n_build"] = b[0].numel()
             st["groups"] = 0
             assert n_out == self.n_probe, (n_out, self.n_probe)
+            self.last_info = {"n_out": n_out}
             return st
         finally:
             op.close()
@@ -384,7 +447,10 @@ class C3:
         self.expected_groups = int(ot * 0.486 * 0.2) + 1024
         self.last_info = None
 
-    def step(self, lib, local_rank, distributed):
+    COUNT_KEYS = ("cust_kept", "orders_kept_scan", "lineitem_kept",
+                  "orders_kept", "joined_rows", "groups")
+
+    def step(self, lib, local_rank, distributed, keep=None):
         from galaxysql_amd.exchange import shuffle_columns
         from galaxysql_amd.queries import (run_q3, run_q3_honest, CUST_TYPES,
                                            ORDERS_TYPES, LINEITEM_TYPES)
@@ -392,7 +458,7 @@ class C3:
             _, info = run_q3_honest(lib, local_rank, self.cust, self.orders,
                                     self.lineitem,
                                     expected_groups=self.expected_groups,
-                                    to_host=False)
+                                    to_host=False, keep_results=keep)
         else:
             (cust, orders, lineitem), scanned = run_q3_honest(
                 lib, local_rank, self.cust, self.orders, self.lineitem,
@@ -406,7 +472,7 @@ class C3:
             _, info = run_q3(lib, local_rank, cust, orders, lineitem,
                              expected_groups=self.expected_groups,
                              to_host=False, reshuffle_by_orderkey=True,
-                             local_rank=local_rank)
+                             local_rank=local_rank, keep_results=keep)
             info.update(scanned)
         self.last_info = info
         st = dict(info["join2_stats"])
@@ -427,6 +493,19 @@ class C3:
                           "revenue projection run on device in the timed step",
                 "exchange": "rccl_all_to_allv" if world > 1 else "none",
                 "parallelism": f"hash_shuffle_dp{world}"}
+
+    def outputs(self, lib, device, kept):
+        import torch
+        from galaxysql_amd.queries import result_to_tensors, Q3_RESULT_TYPES
+        parts = [result_to_tensors(lib, r, Q3_RESULT_TYPES, device)
+                 for r in kept]
+        cols = [torch.cat([p[i] for p in parts])
+                for i in range(len(Q3_RESULT_TYPES))] if parts else []
+        totals = [float(cols[0].numel())] + \
+                 [float(c.sum().item()) for c in cols[3:]] if cols else [0.0] * 4
+        return {"counts": counts_array(self.last_info, self.COUNT_KEYS),
+                "groups": canonical_rows(cols, [0]),
+                "group_totals": np.array(totals)}
 
     def cpu_baseline(self, sample_rows, threads=1):
         return c3_cpu_baseline(sample_scale=1.0 / 128, threads=threads)
@@ -514,7 +593,9 @@ class C4:
         self.expected_groups = no
         self.last_info = None
 
-    def step(self, lib, local_rank, distributed):
+    COUNT_KEYS = ("groups", "survivors", "after_orders", "final_rows")
+
+    def step(self, lib, local_rank, distributed, keep=None):
         from galaxysql_amd.exchange import shuffle_columns
         from galaxysql_amd.queries import (run_q18, Q18_LINEITEM_TYPES,
                                            Q18_ORDERS_TYPES, Q18_CUST_TYPES)
@@ -557,6 +638,9 @@ class C4:
         # 4 wr + 4 rd + record RMW 8 (records[slot] directly — no gid
         # indirection) + l_quantity 8 rd
         return 8 + 4 + 4 + 16 + 0.75 * 8 + 4 + 4 + 8 + 8
+
+    def outputs(self, lib, device, kept):
+        return {"counts": counts_array(self.last_info, self.COUNT_KEYS)}
 
     def cpu_baseline(self, sample_rows, threads=1):
         return c4_cpu_baseline(sample_scale=1.0 / 128, threads=threads)
@@ -674,7 +758,10 @@ class C5:
         self.n_build = ps_part.numel()
         self.last_info = None
 
-    def step(self, lib, local_rank, distributed):
+    COUNT_KEYS = ("part_kept", "partsupp_kept", "lineitem_joined",
+                  "after_orders", "final_rows", "groups")
+
+    def step(self, lib, local_rank, distributed, keep=None):
         from galaxysql_amd.queries import run_q9, stage_table, Q9_PART_TYPES
         if self.part_res is None:
             # one-time device upload of the part table (strings), untimed
@@ -686,6 +773,7 @@ class C5:
                             self.partsupp, self.orders, self.lineitem,
                             world=world, local_rank=local_rank)
         self.last_info = info
+        self.last_rows = rows
         st = dict(info["join2_stats"])
         st["n_build"] = info["partsupp_kept"]
         st["groups"] = info["groups"]
@@ -705,6 +793,11 @@ class C5:
                               "GROUP BY (nation, year), two-phase at N>1",
                 "exchange": "rccl_all_to_allv" if world > 1 else "none",
                 "parallelism": f"hash_shuffle_dp{world}"}
+
+    def outputs(self, lib, device, kept):
+        rows = np.array(sorted(self.last_rows), dtype=np.float64)
+        return {"counts": counts_array(self.last_info, self.COUNT_KEYS),
+                "groups": rows.reshape(-1, 4)}
 
     def cpu_baseline(self, sample_rows, threads=1):
         return c5_cpu_baseline(sample_scale=1.0 / 128, threads=threads)
@@ -776,7 +869,14 @@ def main():
                     help="C4 size fraction of SF100 (1.0 = full)")
     ap.add_argument("--c5-scale", type=float, default=1.0,
                     help="C5 size fraction of the per-GPU SF300/8 shard")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need "
+                         "(the all-cores CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-probe-rows", type=int, default=4_000_000,
                     help="C2 baseline probe rows PER THREAD")
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -819,8 +919,11 @@ def main():
 
     barrier_sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        st = wl.step(lib, local_rank, distributed)
+    kept = []  # --dump-outputs: the last step's device-resident results
+    for i in range(args.steps):
+        last = args.dump_outputs and i == args.steps - 1
+        st = wl.step(lib, local_rank, distributed,
+                     keep=kept if last else None)
         for k in acc:
             acc[k] += st.get(k, 0)
     barrier_sync()
@@ -838,6 +941,17 @@ def main():
     else:
         total_probe_rows_per_step = float(wl.n_probe)
 
+    if args.dump_outputs:
+        try:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            suffix = f".rank{rank}" if rank else ""
+            for name, arr in wl.outputs(lib, device, kept).items():
+                np.save(os.path.join(args.dump_outputs,
+                                     f"{name}{suffix}.npy"), arr)
+        finally:
+            for r in kept:
+                lib.lib.gxop_result_release(r)
+
     if rank != 0:
         return
 
@@ -852,7 +966,7 @@ def main():
     achieved = (bpr * acc["probe_rows"] / (probe_ms / 1e3)) if probe_ms else 0.0
 
     cpu_baseline = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         threads = args.cpu_threads or (os.cpu_count() or 1)
         cpu_baseline = wl.cpu_baseline(args.cpu_probe_rows, threads=threads)
 

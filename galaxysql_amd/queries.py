@@ -28,6 +28,8 @@ from .operators import ParallelHashJoinExec, HashAggExec, EquiJoinKey
 CUST_TYPES = [I64]                       # c_custkey
 ORDERS_TYPES = [I64, I64, I32, I32]      # o_custkey, o_orderkey, o_orderdate, o_shippriority
 LINEITEM_TYPES = [I64, F64, I64]         # l_orderkey, revenue, revenue_cents
+# l_orderkey, o_orderdate, o_shippriority, SUM(revenue), SUM(cents), COUNT(*)
+Q3_RESULT_TYPES = [I64, I32, I32, F64, I64, I64]
 
 
 def _consume_tensors(lib, op, tensors, types):
@@ -98,12 +100,17 @@ def result_to_tensors(lib, res, types, device_t):
 
 
 def run_q3(lib, device, cust, orders, lineitem, expected_groups=0,
-           to_host=True, reshuffle_by_orderkey=False, local_rank=0):
+           to_host=True, reshuffle_by_orderkey=False, local_rank=0,
+           keep_results=None):
     """cust/orders/lineitem: lists of torch tensors (cpu for the oracle,
     cuda for the HIP path) with the column types above.
 
     Returns (result_rows_chunk, info) where info carries join2 kernel stats
-    + intermediate cardinalities. The caller owns nothing to free."""
+    + intermediate cardinalities. The caller owns nothing to free — unless
+    it passes a list as keep_results: with to_host=False the emitted
+    device-resident aggregate batches (gx_result pointers, columns
+    Q3_RESULT_TYPES) are then appended to it instead of released, and the
+    caller releases them."""
     # join1: SEMI — build customer, probe orders on o_custkey
     # (cust/orders/lineitem may be tensor lists or device-resident
     #  gx_results, e.g. scan outputs — run_q3_honest)
@@ -190,7 +197,10 @@ def run_q3(lib, device, cust, orders, lineitem, expected_groups=0,
                         if not out:
                             break
                         n_groups += out.contents.chunk.n_rows
-                        lib.lib.gxop_result_release(out)
+                        if keep_results is not None:
+                            keep_results.append(out)
+                        else:
+                            lib.lib.gxop_result_release(out)
                 info = {"orders_kept": n_orders_kept, "joined_rows": n_joined,
                         "groups": n_groups, "join2_stats": j2_stats}
                 return chunks, info
@@ -216,7 +226,7 @@ Q3_SEGMENT = 0             # c_mktsegment == 0     (1 of 5)
 
 def run_q3_honest(lib, device, raw_cust, raw_orders, raw_lineitem,
                   expected_groups=0, to_host=True, as_tensors=False,
-                  local_rank=0):
+                  local_rank=0, keep_results=None):
     """Q3 with the vectorized filter/projection stage ON DEVICE (SURVEY.md
     §8f row 1): scans filter customer by segment, orders by date, lineitem
     by shipdate — and project revenue = extendedprice*(1-discount) as f64
@@ -261,7 +271,8 @@ def run_q3_honest(lib, device, raw_cust, raw_orders, raw_lineitem,
             return (cust, orders, lineitem), scanned
         chunks, info = run_q3(lib, device, rc, ro, rl,
                               expected_groups=expected_groups,
-                              to_host=to_host, local_rank=local_rank)
+                              to_host=to_host, local_rank=local_rank,
+                              keep_results=keep_results)
         info.update(scanned)
         return chunks, info
     finally:
