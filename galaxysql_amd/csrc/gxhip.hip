@@ -33,21 +33,13 @@
 #include <algorithm>
 #include <cstdlib>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <hipcub/hipcub.hpp>
 
 thread_local std::string gx_err;
 
 /* ================= kernel-side column descriptors ====================== */
-
-static inline size_t gx_fixed_size(int32_t t) {
-    switch (t) {
-    case GX_I64: case GX_F64: return 8;
-    case GX_I32: return 4;
-    case GX_DECIMAL: return 40;
-    default: return 0;
-    }
-}
 
 #define GX_MAX_KEYS 4
 #define GX_MAX_COLS 16
@@ -920,11 +912,6 @@ struct HipResult {
     int device = 0;
 };
 
-static void free_result(HipResult *h) {
-    for (auto &b : h->bufs) b.release();
-    delete h;
-}
-
 /* grid size for memory-bound grid-stride kernels (Guideline 11) */
 static inline int gx_grid(int64_t n, int block = 256) {
     int64_t g = (n + block - 1) / block;
@@ -968,9 +955,10 @@ int ensure_device(int device) {
 /* Build a gx_result from exact-size device buffers. Each column owns a
  * values buf + nulls buf; SLICE columns use slot 0 for END-OFFSETS and a
  * data buf appended later by attach_slice_data (lengths known post-scan). */
-HipResult *alloc_result_cols(const std::vector<int32_t> &types, int64_t n,
-                             int device, hipStream_t stream) {
-    auto *h = new HipResult();
+std::unique_ptr<HipResult> alloc_result_cols(const std::vector<int32_t> &types,
+                                             int64_t n, int device,
+                                             hipStream_t stream) {
+    std::unique_ptr<HipResult> h(new HipResult());
     h->device = device;
     h->blocks.resize(types.size());
     h->bufs.resize(types.size() * 2);
@@ -978,10 +966,8 @@ HipResult *alloc_result_cols(const std::vector<int32_t> &types, int64_t n,
         size_t es = types[c] == GX_SLICE ? 4 : gx_fixed_size(types[c]);
         if (n > 0) {
             if (h->bufs[c * 2].grow((size_t)n * es, stream) ||
-                h->bufs[c * 2 + 1].grow((size_t)n, stream)) {
-                free_result(h);
+                h->bufs[c * 2 + 1].grow((size_t)n, stream))
                 return nullptr;
-            }
         }
         gx_block &b = h->blocks[c];
         std::memset(&b, 0, sizeof(b));
@@ -996,8 +982,56 @@ HipResult *alloc_result_cols(const std::vector<int32_t> &types, int64_t n,
     h->res.chunk.n_rows = (int32_t)n;
     h->res.chunk.n_blocks = (int32_t)types.size();
     h->res.chunk.blocks = h->blocks.data();
-    h->res.opaque = h;
+    h->res.opaque = h.get();
     return h;
+}
+
+/* hand a finished result to the C-ABI caller; gxop_result_release deletes it */
+void give_result(std::unique_ptr<HipResult> h, gx_result **out) {
+    *out = &h.release()->res;
+}
+
+/* hipcub's two-call protocol: `call(tmp, bytes)` runs once with tmp ==
+ * nullptr to learn the scratch size, then again with `tmp` grown to it. */
+template <class F>
+int cub_run(DevBuf &tmp, hipStream_t stream, F &&call) {
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e == hipSuccess && tmp.grow(bytes, stream)) return -1;
+    if (e == hipSuccess) e = call(tmp.p, bytes);
+    if (e != hipSuccess) {
+        gx_set_err(std::string("hipcub: ") + hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
+/* inclusive sum of in[0..n) into out, then fetch out[n-1] to the host
+ * (synchronizes the stream). n > 0. */
+template <class In, class T, class N>
+int cub_inclusive_sum_total(DevBuf &tmp, hipStream_t stream, In in, T *out,
+                            N n, T *total) {
+    if (cub_run(tmp, stream, [&](void *t, size_t &b) {
+            return hipcub::DeviceScan::InclusiveSum(t, b, in, out, n, stream);
+        }))
+        return -1;
+    HIP_OK(hipMemcpyAsync(total, out + (n - 1), sizeof(T),
+                          hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+/* describe a device-resident column as a gx_block (borrowed pointers) */
+gx_block view_block(const DevColView &v) {
+    gx_block b;
+    std::memset(&b, 0, sizeof(b));
+    b.type = v.type;
+    b.mem = GX_MEM_DEVICE;
+    b.values = v.values;
+    b.nulls = v.has_nulls ? v.nulls : nullptr;
+    b.offsets = v.offsets;
+    b.data = v.bytes;
+    return b;
 }
 
 /* allocate and register the byte payload for a SLICE result column */
@@ -1021,16 +1055,8 @@ int gather_slice_col(const DevColView &src, const uint32_t *idx,
     uint8_t *nulls = (uint8_t *)h->bufs[col * 2 + 1].p;
     hipLaunchKernelGGL(k_slice_lens, dim3(gx_grid(n)), dim3(256), 0, stream,
                        src, idx, fill_null_only, n, off, nulls);
-    size_t tmp_bytes = 0;
-    HIP_OK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, off, off, n,
-                                            stream));
-    if (scan_tmp.grow(tmp_bytes, stream)) return -1;
-    HIP_OK(hipcub::DeviceScan::InclusiveSum(scan_tmp.p, tmp_bytes, off, off,
-                                            n, stream));
     int32_t total = 0;
-    HIP_OK(hipMemcpyAsync(&total, off + (n - 1), 4, hipMemcpyDeviceToHost,
-                          stream));
-    HIP_OK(hipStreamSynchronize(stream));
+    if (cub_inclusive_sum_total(scan_tmp, stream, off, off, n, &total)) return -1;
     if (attach_slice_data(h, col, total, stream)) return -1;
     if (total > 0)
         hipLaunchKernelGGL(k_slice_copy, dim3(gx_grid(n)), dim3(256), 0,
@@ -1039,12 +1065,52 @@ int gather_slice_col(const DevColView &src, const uint32_t *idx,
     return 0;
 }
 
+/* pass-through: copy the n-row input columns views[0..types.size()) into
+ * the leading result columns. Fixed-width: D2D copy of values and nulls
+ * (zeros when the source has none); SLICE: identity gather (copies offsets
+ * + bytes). */
+int copy_input_cols(const std::vector<int32_t> &types, const DevColView *views,
+                    int64_t n, HipResult *h, DevBuf &scan_tmp,
+                    hipStream_t stream) {
+    for (size_t c = 0; c < types.size(); c++) {
+        const DevColView &v = views[c];
+        if (types[c] == GX_SLICE) {
+            if (gather_slice_col(v, nullptr, 0, n, h, c, scan_tmp, stream))
+                return -1;
+            continue;
+        }
+        HIP_OK(hipMemcpyAsync(h->bufs[c * 2].p, v.values,
+                              (size_t)n * gx_fixed_size(types[c]),
+                              hipMemcpyDeviceToDevice, stream));
+        if (v.nulls)
+            HIP_OK(hipMemcpyAsync(h->bufs[c * 2 + 1].p, v.nulls, (size_t)n,
+                                  hipMemcpyDeviceToDevice, stream));
+        else
+            HIP_OK(hipMemsetAsync(h->bufs[c * 2 + 1].p, 0, (size_t)n, stream));
+    }
+    return 0;
+}
+
 /* stage an input chunk: if every block is device-resident we use the
- * caller's pointers directly (zero copy); otherwise copy host->device. */
+ * caller's pointers directly (zero copy); otherwise copy host->device into
+ * buffers the StagedChunk owns until it goes out of scope. */
 struct StagedChunk {
     std::vector<DevBuf> owned;
     std::vector<DevColView> views;
     int64_t n_rows = 0;
+
+    /* copy `bytes` host bytes into a new owned buffer (of at least
+     * min_cap bytes) and point dst at it */
+    template <class T>
+    int upload(const T *src, size_t bytes, hipStream_t stream, const T *&dst,
+               size_t min_cap = 0) {
+        owned.emplace_back();
+        DevBuf &d = owned.back();
+        if (d.grow(std::max(bytes, min_cap), stream)) return -1;
+        HIP_OK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, stream));
+        dst = (const T *)d.p;
+        return 0;
+    }
 
     int stage(const gx_chunk *ch, hipStream_t stream) {
         n_rows = ch->n_rows;
@@ -1053,67 +1119,33 @@ struct StagedChunk {
             const gx_block *b = &ch->blocks[c];
             DevColView &v = views[c];
             v.type = b->type;
+            v.has_nulls = b->nulls != nullptr;
+            v.values = nullptr; v.nulls = nullptr;
             v.offsets = nullptr; v.bytes = nullptr;
-            if (b->type == GX_SLICE) {
-                v.has_nulls = b->nulls != nullptr;
-                if (b->mem == GX_MEM_DEVICE) {
+            if (b->mem == GX_MEM_DEVICE) {
+                v.nulls = (const uint8_t *)b->nulls;
+                if (b->type == GX_SLICE) {
                     v.offsets = b->offsets;
                     v.bytes = b->data;
-                    v.nulls = (const uint8_t *)b->nulls;
                 } else {
-                    int64_t blen = n_rows > 0 ? b->offsets[n_rows - 1] : 0;
-                    owned.emplace_back();
-                    DevBuf &ob = owned.back();
-                    if (ob.grow((size_t)std::max<int64_t>(n_rows, 1) * 4, stream)) return -1;
-                    HIP_OK(hipMemcpyAsync(ob.p, b->offsets, (size_t)n_rows * 4,
-                                          hipMemcpyHostToDevice, stream));
-                    v.offsets = (const int32_t *)ob.p;
-                    owned.emplace_back();
-                    DevBuf &db = owned.back();
-                    if (blen > 0) {
-                        if (db.grow((size_t)blen, stream)) return -1;
-                        HIP_OK(hipMemcpyAsync(db.p, b->data, (size_t)blen,
-                                              hipMemcpyHostToDevice, stream));
-                    }
-                    v.bytes = (const uint8_t *)db.p;
-                    if (b->nulls) {
-                        owned.emplace_back();
-                        DevBuf &nb = owned.back();
-                        if (nb.grow((size_t)n_rows, stream)) return -1;
-                        HIP_OK(hipMemcpyAsync(nb.p, b->nulls, (size_t)n_rows,
-                                              hipMemcpyHostToDevice, stream));
-                        v.nulls = (const uint8_t *)nb.p;
-                    }
+                    v.values = b->values;
                 }
                 continue;
             }
-            size_t es = gx_fixed_size(b->type);
-            if (b->mem == GX_MEM_DEVICE) {
-                v.values = b->values;
-                v.nulls = (const uint8_t *)b->nulls;
-                v.has_nulls = b->nulls != nullptr;
-            } else {
-                owned.emplace_back();
-                DevBuf &vb = owned.back();
-                if (vb.grow((size_t)n_rows * es, stream)) return -1;
-                HIP_OK(hipMemcpyAsync(vb.p, b->values, (size_t)n_rows * es,
-                                      hipMemcpyHostToDevice, stream));
-                v.values = vb.p;
-                v.has_nulls = b->nulls != nullptr;
-                v.nulls = nullptr;
-                if (b->nulls) {
-                    owned.emplace_back();
-                    DevBuf &nb = owned.back();
-                    if (nb.grow((size_t)n_rows, stream)) return -1;
-                    HIP_OK(hipMemcpyAsync(nb.p, b->nulls, (size_t)n_rows,
-                                          hipMemcpyHostToDevice, stream));
-                    v.nulls = (const uint8_t *)nb.p;
-                }
+            const size_t n = (size_t)n_rows;
+            if (b->type == GX_SLICE) {
+                int64_t blen = n_rows > 0 ? b->offsets[n_rows - 1] : 0;
+                if (upload(b->offsets, n * 4, stream, v.offsets, 4)) return -1;
+                if (blen > 0 &&
+                    upload(b->data, (size_t)blen, stream, v.bytes)) return -1;
+            } else if (upload(b->values, n * gx_fixed_size(b->type), stream,
+                              v.values)) {
+                return -1;
             }
+            if (b->nulls && upload(b->nulls, n, stream, v.nulls)) return -1;
         }
         return 0;
     }
-    void release() { for (auto &b : owned) b.release(); owned.clear(); }
 };
 
 /* ========================= JoinOp ====================================== */
@@ -1123,22 +1155,24 @@ struct JoinOp : gx_op {
     std::vector<gx_equi_key> keys;
     std::vector<gx_join_cond> conds;             /* residual condition */
     std::vector<std::vector<uint8_t>> cond_bytes; /* deep-copied SLICE consts */
-    std::vector<DevBuf> d_cond_pats;
     std::vector<int32_t> out_proj;  /* projection pushdown; empty = full */
     std::vector<int32_t> outer_types, inner_types;
     std::vector<int> build_key_cols, probe_key_cols;
 
-    DevStore build;          /* build-side columns in HBM */
+    /* device buffers, last-allocated first (see DevBuf: destruction order
+     * and the pool) */
+    std::vector<DevBuf> d_cond_pats;
+    DevBuf d_bloom;            /* blocked bloom pre-filter (fast path) */
+    DevBuf d_radix_cnt, d_staged;               /* radix-staged probe rows */
+    DevBuf d_pn, d_ph, d_meta, d_bpos, d_pidx; /* reused across probe calls */
+    DevBuf d_scan_tmp;
+    DevBuf d_bitmap;         /* build_outer matched bitmap */
+    DevBuf d_entries, d_starts, d_counts; /* CSR (null_safe) / IB overflow */
+    DevBuf d_keynull, d_hashes;
+    DevBuf d_table;          /* inline-bucket table (plain joins) */
     DevStore probe_buf;      /* buffered-probe staging (probe_push/flush) */
     bool probe_buf_init = false;
-    DevBuf d_hashes, d_keynull;
-    DevBuf d_table;          /* inline-bucket table (plain joins) */
-    DevBuf d_counts, d_starts, d_entries; /* CSR (null_safe) / IB overflow */
-    DevBuf d_bitmap;         /* build_outer matched bitmap */
-    DevBuf d_scan_tmp;
-    DevBuf d_pidx, d_bpos, d_meta, d_ph, d_pn; /* reused across probe calls */
-    DevBuf d_staged, d_radix_cnt;               /* radix-staged probe rows */
-    DevBuf d_bloom;            /* blocked bloom pre-filter (fast path) */
+    DevStore build;          /* build-side columns in HBM */
     uint32_t bloom_mask = 0;
     uint32_t mask = 0;
     int64_t n_buckets = 0;
@@ -1181,17 +1215,6 @@ struct JoinOp : gx_op {
         if (cfg.expected_build_rows > 0) build.reserve(cfg.expected_build_rows);
     }
     ~JoinOp() override {
-        build.release();
-        probe_buf.release();
-        d_table.release();
-        d_hashes.release(); d_keynull.release(); d_counts.release();
-        d_starts.release(); d_entries.release(); d_bitmap.release();
-        d_scan_tmp.release();
-        d_pidx.release(); d_bpos.release(); d_meta.release();
-        d_ph.release(); d_pn.release();
-        d_staged.release(); d_radix_cnt.release();
-        d_bloom.release();
-        for (auto &b : d_cond_pats) b.release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
     }
@@ -1301,16 +1324,12 @@ struct JoinOp : gx_op {
                                    (const int32_t *)d_hashes.p, (const uint8_t *)d_keynull.p,
                                    n, (uint32_t *)d_counts.p, mask);
                 /* exclusive scan counts[0..n_buckets] -> starts (incl. total) */
-                size_t tmp_bytes = 0;
-                HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes,
-                                                        (uint32_t *)d_counts.p,
-                                                        (uint32_t *)d_starts.p,
-                                                        n_buckets + 1, stream));
-                if (d_scan_tmp.grow(tmp_bytes, stream)) return -1;
-                HIP_OK(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tmp_bytes,
-                                                        (uint32_t *)d_counts.p,
-                                                        (uint32_t *)d_starts.p,
-                                                        n_buckets + 1, stream));
+                if (cub_run(d_scan_tmp, stream, [&](void *t, size_t &b) {
+                        return hipcub::DeviceScan::ExclusiveSum(
+                            t, b, (uint32_t *)d_counts.p, (uint32_t *)d_starts.p,
+                            n_buckets + 1, stream);
+                    }))
+                    return -1;
                 /* reuse counts as cursors (= starts) */
                 HIP_OK(hipMemcpyAsync(d_counts.p, d_starts.p, (size_t)n_buckets * 4,
                                       hipMemcpyDeviceToDevice, stream));
@@ -1341,16 +1360,12 @@ struct JoinOp : gx_op {
                 hipLaunchKernelGGL(k_ovf_counts, dim3(gx_grid(n_buckets)), dim3(256),
                                    0, stream, (const uint32_t *)d_counts.p,
                                    n_buckets, (uint32_t *)d_starts.p);
-                size_t tmp_bytes = 0;
-                HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes,
-                                                        (uint32_t *)d_starts.p,
-                                                        (uint32_t *)d_starts.p,
-                                                        n_buckets + 1, stream));
-                if (d_scan_tmp.grow(tmp_bytes, stream)) return -1;
-                HIP_OK(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tmp_bytes,
-                                                        (uint32_t *)d_starts.p,
-                                                        (uint32_t *)d_starts.p,
-                                                        n_buckets + 1, stream));
+                if (cub_run(d_scan_tmp, stream, [&](void *t, size_t &b) {
+                        return hipcub::DeviceScan::ExclusiveSum(
+                            t, b, (uint32_t *)d_starts.p, (uint32_t *)d_starts.p,
+                            n_buckets + 1, stream);
+                    }))
+                    return -1;
                 uint32_t total_ovf = 0;
                 HIP_OK(hipMemcpyAsync(&total_ovf,
                                       (uint32_t *)d_starts.p + n_buckets, 4,
@@ -1408,7 +1423,6 @@ struct JoinOp : gx_op {
             uint32_t f = 0;
             HIP_OK(hipMemcpyAsync(&f, flag.p, 4, hipMemcpyDeviceToHost, stream));
             HIP_OK(hipStreamSynchronize(stream));
-            flag.release();
             if (f) pass_nothing = true;
         }
 
@@ -1464,13 +1478,14 @@ struct JoinOp : gx_op {
     }
 
     /* gather output columns for a pair list into a new result */
-    HipResult *materialize(const StagedChunk &probe, const uint32_t *d_pidx,
-                           const uint32_t *d_bpos, int64_t n_out) {
+    std::unique_ptr<HipResult> materialize(const StagedChunk &probe,
+                                           const uint32_t *d_pidx,
+                                           const uint32_t *d_bpos,
+                                           int64_t n_out) {
         std::vector<int32_t> otypes = output_types();
         if (otypes.size() > GX_MAX_COLS) { gx_set_err("too many output cols"); return nullptr; }
-        HipResult *h = alloc_result_cols(otypes, n_out, device, stream);
-        if (!h) return nullptr;
-        if (n_out == 0) return h;
+        auto h = alloc_result_cols(otypes, n_out, device, stream);
+        if (!h || n_out == 0) return h;
 
         GatherParams G;
         std::memset(&G, 0, sizeof(G));
@@ -1512,11 +1527,9 @@ struct JoinOp : gx_op {
                                0, stream, G);
         for (auto &sj : slice_jobs) {
             if (gather_slice_col(sj.src, sj.null_fill ? nullptr : sj.idx,
-                                 sj.null_fill, n_out, h, sj.col, d_scan_tmp,
-                                 stream)) {
-                free_result(h);
+                                 sj.null_fill, n_out, h.get(), sj.col,
+                                 d_scan_tmp, stream))
                 return nullptr;
-            }
         }
         return h;
     }
@@ -1531,10 +1544,9 @@ struct JoinOp : gx_op {
         const int64_t n = probe_st.n_rows;
 
         if (pass_nothing || n == 0) {
-            HipResult *h = alloc_result_cols(output_types(), 0, device, stream);
-            if (!h) { probe_st.release(); return -1; }
-            *out = &h->res;
-            probe_st.release();
+            auto h = alloc_result_cols(output_types(), 0, device, stream);
+            if (!h) return -1;
+            give_result(std::move(h), out);
             return 0;
         }
 
@@ -1550,193 +1562,186 @@ struct JoinOp : gx_op {
                                (uint8_t *)d_pn.p, (int)null_safe_keys);
         }
 
-        int rc = -1;
-        do {
-            if (pass_through) {
-                /* ANTI over empty build: all probe rows pass */
-                if (d_pidx.grow((size_t)n * 4, stream)) break;
-                hipLaunchKernelGGL(k_iota, dim3(gx_grid(n)), dim3(256), 0, stream,
-                                   (uint32_t *)d_pidx.p, n);
-                HipResult *h = materialize(probe_st, (uint32_t *)d_pidx.p,
-                                           nullptr, n);
-                if (!h) break;
-                HIP_OK(hipStreamSynchronize(stream));
-                *out = &h->res;
-                rc = 0;
-                break;
-            }
+        if (pass_through) {
+            /* ANTI over empty build: all probe rows pass */
+            if (d_pidx.grow((size_t)n * 4, stream)) return -1;
+            hipLaunchKernelGGL(k_iota, dim3(gx_grid(n)), dim3(256), 0, stream,
+                               (uint32_t *)d_pidx.p, n);
+            auto h = materialize(probe_st, (uint32_t *)d_pidx.p, nullptr, n);
+            if (!h) return -1;
+            HIP_OK(hipStreamSynchronize(stream));
+            give_result(std::move(h), out);
+            return 0;
+        }
 
-            uint32_t cap = (uint32_t)std::min<int64_t>(
-                std::max<int64_t>((int64_t)n * 2, 1 << 16), INT64_C(1) << 31);
-            if (d_meta.grow(8, stream)) break;
+        uint32_t cap = (uint32_t)std::min<int64_t>(
+            std::max<int64_t>((int64_t)n * 2, 1 << 16), INT64_C(1) << 31);
+        if (d_meta.grow(8, stream)) return -1;
 
-            /* Bucket-clustered staging (fast path): partition the probe
-             * rows so each workgroup probes one ~2 MB bucket-range slice.
-             * MEASURED OFF by default (r2 A/B, GX_RADIX=1 forces): the
-             * ~2.5 probes/bucket do stop refetching HBM lines, but the
-             * 30+ concurrent workgroups per XCD each hold a DIFFERENT
-             * 2 MB slice — 60+ MB of hot slices against 4 MB of XCD L2 —
-             * so the slices thrash each other and the staged probe ran
-             * 15.5 ms vs 11.0 ms unstaged (plus a 6.1 ms scatter).
-             * Making concurrent slices fit L2 needs <=128 KB slices
-             * (64K partitions, two-level scatter) — not attempted. */
-            const int64_t table_bytes = n_buckets * 4 * (int64_t)sizeof(JoinEntry);
-            int64_t n_part_radix = 1;
-            int radix_shift = 0;
-            const char *radix_env = getenv("GX_RADIX");
-            bool use_radix = fast_i64 && radix_env && radix_env[0] == '1';
-            (void)table_bytes;
-            if (use_radix) {
-                const int64_t slice = 2 << 20;
-                n_part_radix = gx_pow2((table_bytes + slice - 1) / slice);
-                if (n_part_radix > GX_RADIX_MAXP) n_part_radix = GX_RADIX_MAXP;
-                if (n_part_radix > n_buckets) n_part_radix = 1;
-                while ((1 << radix_shift) < n_buckets / n_part_radix)
-                    radix_shift++;
-            }
-            std::vector<uint32_t> radix_starts;
-            if (n_part_radix > 1) {
-                if (d_staged.grow((size_t)n * sizeof(RadixRow), stream) ||
-                    d_radix_cnt.grow((size_t)(n_part_radix + 1) * 4, stream))
-                    break;
-                HIP_OK(hipMemsetAsync(d_radix_cnt.p, 0, (size_t)n_part_radix * 4,
-                                      stream));
-                hipLaunchKernelGGL(k_radix_count, dim3(gx_grid(n)), dim3(256), 0,
-                                   stream, pk.col[0], n, mask, radix_shift,
-                                   (int)n_part_radix, (uint32_t *)d_radix_cnt.p);
-                std::vector<uint32_t> counts((size_t)n_part_radix);
-                HIP_OK(hipMemcpyAsync(counts.data(), d_radix_cnt.p,
-                                      (size_t)n_part_radix * 4,
-                                      hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipStreamSynchronize(stream));
-                radix_starts.assign((size_t)n_part_radix + 1, 0);
-                for (int64_t p = 0; p < n_part_radix; p++)
-                    radix_starts[p + 1] = radix_starts[p] + counts[p];
-                HIP_OK(hipMemcpyAsync(d_radix_cnt.p, radix_starts.data(),
-                                      (size_t)n_part_radix * 4,
-                                      hipMemcpyHostToDevice, stream));
-                hipLaunchKernelGGL(k_radix_scatter,
-                                   dim3(gx_grid((n + GX_RADIX_TILE - 1) /
-                                                GX_RADIX_TILE * 256) ),
-                                   dim3(256), 0, stream,
-                                   pk.col[0], n, mask, radix_shift,
-                                   (int)n_part_radix,
-                                   (uint32_t *)d_radix_cnt.p,
-                                   (RadixRow *)d_staged.p);
-                /* cursors now hold end offsets == starts[1..n]; rebuild the
-                 * starts array (incl. leading 0) for the probe kernel */
-                HIP_OK(hipMemcpyAsync(d_radix_cnt.p, radix_starts.data(),
-                                      (size_t)(n_part_radix + 1) * 4,
-                                      hipMemcpyHostToDevice, stream));
-            }
+        /* Bucket-clustered staging (fast path): partition the probe
+         * rows so each workgroup probes one ~2 MB bucket-range slice.
+         * MEASURED OFF by default (r2 A/B, GX_RADIX=1 forces): the
+         * ~2.5 probes/bucket do stop refetching HBM lines, but the
+         * 30+ concurrent workgroups per XCD each hold a DIFFERENT
+         * 2 MB slice — 60+ MB of hot slices against 4 MB of XCD L2 —
+         * so the slices thrash each other and the staged probe ran
+         * 15.5 ms vs 11.0 ms unstaged (plus a 6.1 ms scatter).
+         * Making concurrent slices fit L2 needs <=128 KB slices
+         * (64K partitions, two-level scatter) — not attempted. */
+        const int64_t table_bytes = n_buckets * 4 * (int64_t)sizeof(JoinEntry);
+        int64_t n_part_radix = 1;
+        int radix_shift = 0;
+        const char *radix_env = getenv("GX_RADIX");
+        bool use_radix = fast_i64 && radix_env && radix_env[0] == '1';
+        (void)table_bytes;
+        if (use_radix) {
+            const int64_t slice = 2 << 20;
+            n_part_radix = gx_pow2((table_bytes + slice - 1) / slice);
+            if (n_part_radix > GX_RADIX_MAXP) n_part_radix = GX_RADIX_MAXP;
+            if (n_part_radix > n_buckets) n_part_radix = 1;
+            while ((1 << radix_shift) < n_buckets / n_part_radix)
+                radix_shift++;
+        }
+        std::vector<uint32_t> radix_starts;
+        if (n_part_radix > 1) {
+            if (d_staged.grow((size_t)n * sizeof(RadixRow), stream) ||
+                d_radix_cnt.grow((size_t)(n_part_radix + 1) * 4, stream))
+                return -1;
+            HIP_OK(hipMemsetAsync(d_radix_cnt.p, 0, (size_t)n_part_radix * 4,
+                                  stream));
+            hipLaunchKernelGGL(k_radix_count, dim3(gx_grid(n)), dim3(256), 0,
+                               stream, pk.col[0], n, mask, radix_shift,
+                               (int)n_part_radix, (uint32_t *)d_radix_cnt.p);
+            std::vector<uint32_t> counts((size_t)n_part_radix);
+            HIP_OK(hipMemcpyAsync(counts.data(), d_radix_cnt.p,
+                                  (size_t)n_part_radix * 4,
+                                  hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            radix_starts.assign((size_t)n_part_radix + 1, 0);
+            for (int64_t p = 0; p < n_part_radix; p++)
+                radix_starts[p + 1] = radix_starts[p] + counts[p];
+            HIP_OK(hipMemcpyAsync(d_radix_cnt.p, radix_starts.data(),
+                                  (size_t)n_part_radix * 4,
+                                  hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL(k_radix_scatter,
+                               dim3(gx_grid((n + GX_RADIX_TILE - 1) /
+                                            GX_RADIX_TILE * 256) ),
+                               dim3(256), 0, stream,
+                               pk.col[0], n, mask, radix_shift,
+                               (int)n_part_radix,
+                               (uint32_t *)d_radix_cnt.p,
+                               (RadixRow *)d_staged.p);
+            /* cursors now hold end offsets == starts[1..n]; rebuild the
+             * starts array (incl. leading 0) for the probe kernel */
+            HIP_OK(hipMemcpyAsync(d_radix_cnt.p, radix_starts.data(),
+                                  (size_t)(n_part_radix + 1) * 4,
+                                  hipMemcpyHostToDevice, stream));
+        }
 
-            for (int attempt = 0; attempt < 4; attempt++) {
-                if (d_pidx.grow((size_t)cap * 4, stream) ||
-                    d_bpos.grow((size_t)cap * 4, stream)) { attempt = 99; break; }
-                HIP_OK(hipMemsetAsync(d_meta.p, 0, 8, stream));
-                ProbeParams P;
-                P.table = (const JoinEntry *)d_table.p;
-                P.entries = (const JoinEntry *)d_entries.p;
-                P.mask = mask;
-                P.n_probe = n;
-                P.hashes = (const int32_t *)d_ph.p;
-                P.keynull = (const uint8_t *)d_pn.p;
-                P.staged = nullptr;
-                P.part_starts = nullptr;
-                P.n_parts = 0;
-                P.bloom = (const uint32_t *)d_bloom.p;
-                P.bloom_mask = bloom_mask;
-                P.fast_i64 = (int)fast_i64;
-                P.build_keys = key_views(build, build_key_cols);
-                P.probe_keys = pk;
-                P.join_type = cfg.join_type;
-                P.semi_join = (cfg.join_type == GX_JOIN_SEMI ||
-                               cfg.join_type == GX_JOIN_ANTI) && !cfg.single_join;
-                P.outer_join = cfg.join_type == GX_JOIN_LEFT ||
-                               cfg.join_type == GX_JOIN_RIGHT;
-                P.single_join = cfg.single_join;
-                P.build_outer = cfg.build_outer;
-                P.anti_null_col = cfg.anti_null_col;
-                if (cfg.anti_null_col >= 0)
-                    P.anti_col = probe_st.views[cfg.anti_null_col];
-                else
-                    std::memset(&P.anti_col, 0, sizeof(P.anti_col));
-                P.out_probe = (uint32_t *)d_pidx.p;
-                P.out_build = (uint32_t *)d_bpos.p;
-                P.cap = cap;
-                P.counter = (uint32_t *)d_meta.p;
-                P.err = (uint32_t *)d_meta.p + 1;
-                P.build_matched = cfg.build_outer ? (uint32_t *)d_bitmap.p : nullptr;
-                P.n_conds = (int32_t)conds.size();
-                if (!conds.empty() && upload_cond_pats()) { attempt = 99; break; }
-                for (size_t t = 0; t < conds.size(); t++) {
-                    const gx_join_cond &src = conds[t];
-                    JoinCondDev &d = P.conds[t];
-                    std::memset(&d, 0, sizeof(d));
-                    d.cmp = src.cmp;
-                    d.const_is_null = src.const_is_null;
-                    bool a_build = false, b_build = false;
-                    int a_src = cond_map(src.col_a, a_build);
-                    d.a_is_build = a_build;
-                    d.a = a_build ? build.view(a_src) : probe_st.views[a_src];
-                    d.b_is_const = src.col_b < 0;
-                    if (d.b_is_const) {
-                        d.v_i64 = src.v_i64;
-                        d.v_f64 = src.v_f64;
-                        d.v_bytes = (const uint8_t *)d_cond_pats[t].p;
-                        d.v_len = src.v_len;
-                    } else {
-                        int b_src = cond_map(src.col_b, b_build);
-                        d.b_is_build = b_build;
-                        d.b = b_build ? build.view(b_src) : probe_st.views[b_src];
-                    }
-                }
-                if (!ev0) {
-                    HIP_OK(hipEventCreate(&ev0));
-                    HIP_OK(hipEventCreate(&ev1));
-                }
-                HIP_OK(hipEventRecord(ev0, stream));
-                if (n_part_radix > 1) {
-                    P.staged = (const RadixRow *)d_staged.p;
-                    P.part_starts = (const uint32_t *)d_radix_cnt.p;
-                    P.n_parts = (int32_t)n_part_radix;
-                    hipLaunchKernelGGL(k_probe, dim3((uint32_t)n_part_radix),
-                                       dim3(256), 0, stream, P);
+        for (int attempt = 0; attempt < 4; attempt++) {
+            if (d_pidx.grow((size_t)cap * 4, stream) ||
+                d_bpos.grow((size_t)cap * 4, stream)) return -1;
+            HIP_OK(hipMemsetAsync(d_meta.p, 0, 8, stream));
+            ProbeParams P;
+            P.table = (const JoinEntry *)d_table.p;
+            P.entries = (const JoinEntry *)d_entries.p;
+            P.mask = mask;
+            P.n_probe = n;
+            P.hashes = (const int32_t *)d_ph.p;
+            P.keynull = (const uint8_t *)d_pn.p;
+            P.staged = nullptr;
+            P.part_starts = nullptr;
+            P.n_parts = 0;
+            P.bloom = (const uint32_t *)d_bloom.p;
+            P.bloom_mask = bloom_mask;
+            P.fast_i64 = (int)fast_i64;
+            P.build_keys = key_views(build, build_key_cols);
+            P.probe_keys = pk;
+            P.join_type = cfg.join_type;
+            P.semi_join = (cfg.join_type == GX_JOIN_SEMI ||
+                           cfg.join_type == GX_JOIN_ANTI) && !cfg.single_join;
+            P.outer_join = cfg.join_type == GX_JOIN_LEFT ||
+                           cfg.join_type == GX_JOIN_RIGHT;
+            P.single_join = cfg.single_join;
+            P.build_outer = cfg.build_outer;
+            P.anti_null_col = cfg.anti_null_col;
+            if (cfg.anti_null_col >= 0)
+                P.anti_col = probe_st.views[cfg.anti_null_col];
+            else
+                std::memset(&P.anti_col, 0, sizeof(P.anti_col));
+            P.out_probe = (uint32_t *)d_pidx.p;
+            P.out_build = (uint32_t *)d_bpos.p;
+            P.cap = cap;
+            P.counter = (uint32_t *)d_meta.p;
+            P.err = (uint32_t *)d_meta.p + 1;
+            P.build_matched = cfg.build_outer ? (uint32_t *)d_bitmap.p : nullptr;
+            P.n_conds = (int32_t)conds.size();
+            if (!conds.empty() && upload_cond_pats()) return -1;
+            for (size_t t = 0; t < conds.size(); t++) {
+                const gx_join_cond &src = conds[t];
+                JoinCondDev &d = P.conds[t];
+                std::memset(&d, 0, sizeof(d));
+                d.cmp = src.cmp;
+                d.const_is_null = src.const_is_null;
+                bool a_build = false, b_build = false;
+                int a_src = cond_map(src.col_a, a_build);
+                d.a_is_build = a_build;
+                d.a = a_build ? build.view(a_src) : probe_st.views[a_src];
+                d.b_is_const = src.col_b < 0;
+                if (d.b_is_const) {
+                    d.v_i64 = src.v_i64;
+                    d.v_f64 = src.v_f64;
+                    d.v_bytes = (const uint8_t *)d_cond_pats[t].p;
+                    d.v_len = src.v_len;
                 } else {
-                    hipLaunchKernelGGL(k_probe, dim3(gx_grid(n)), dim3(256), 0,
-                                       stream, P);
+                    int b_src = cond_map(src.col_b, b_build);
+                    d.b_is_build = b_build;
+                    d.b = b_build ? build.view(b_src) : probe_st.views[b_src];
                 }
-                HIP_OK(hipEventRecord(ev1, stream));
-                uint32_t meta[2];
-                HIP_OK(hipMemcpyAsync(meta, d_meta.p, 8, hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipStreamSynchronize(stream));
-                if (meta[1]) {
-                    gx_set_err("ERR_SCALAR_SUBQUERY_RETURN_MORE_THAN_ONE_ROW");
-                    probe_st.release();
-                    return -2;
-                }
-                {
-                    float ms = 0;
-                    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-                    probe_kernel_ms += ms;
-                    probe_launches++;
-                }
-                if (meta[0] <= cap) {
-                    probe_rows_total += n;
-                    matches_total += meta[0];
-                    HipResult *h = materialize(probe_st, (uint32_t *)d_pidx.p,
-                                               (uint32_t *)d_bpos.p, meta[0]);
-                    if (!h) { attempt = 99; break; }
-                    HIP_OK(hipStreamSynchronize(stream));
-                    *out = &h->res;
-                    rc = 0;
-                    break;
-                }
-                cap = meta[0]; /* retry with exact size */
             }
-        } while (0);
-        probe_st.release();
-        return rc;
+            if (!ev0) {
+                HIP_OK(hipEventCreate(&ev0));
+                HIP_OK(hipEventCreate(&ev1));
+            }
+            HIP_OK(hipEventRecord(ev0, stream));
+            if (n_part_radix > 1) {
+                P.staged = (const RadixRow *)d_staged.p;
+                P.part_starts = (const uint32_t *)d_radix_cnt.p;
+                P.n_parts = (int32_t)n_part_radix;
+                hipLaunchKernelGGL(k_probe, dim3((uint32_t)n_part_radix),
+                                   dim3(256), 0, stream, P);
+            } else {
+                hipLaunchKernelGGL(k_probe, dim3(gx_grid(n)), dim3(256), 0,
+                                   stream, P);
+            }
+            HIP_OK(hipEventRecord(ev1, stream));
+            uint32_t meta[2];
+            HIP_OK(hipMemcpyAsync(meta, d_meta.p, 8, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            if (meta[1]) {
+                gx_set_err("ERR_SCALAR_SUBQUERY_RETURN_MORE_THAN_ONE_ROW");
+                return -2;
+            }
+            {
+                float ms = 0;
+                HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
+                probe_kernel_ms += ms;
+                probe_launches++;
+            }
+            if (meta[0] <= cap) {
+                probe_rows_total += n;
+                matches_total += meta[0];
+                auto h = materialize(probe_st, (uint32_t *)d_pidx.p,
+                                     (uint32_t *)d_bpos.p, meta[0]);
+                if (!h) return -1;
+                /* the staged probe chunk is freed on return: drain first */
+                HIP_OK(hipStreamSynchronize(stream));
+                give_result(std::move(h), out);
+                return 0;
+            }
+            cap = meta[0]; /* retry with exact size */
+        }
+        return -1; /* pair list still short after 4 resizes */
     }
 
     /* Buffered probe (gxop.h: the LocalBufferExec pattern): push appends
@@ -1762,22 +1767,13 @@ struct JoinOp : gx_op {
             gx_set_err("buffered probe exceeds 2^31 rows; flush earlier");
             return -1;
         }
-        std::vector<gx_block> blocks(probe_buf.cols.size());
-        for (size_t c = 0; c < probe_buf.cols.size(); c++) {
-            DevColView v = probe_buf.view((int32_t)c);
-            gx_block &b = blocks[c];
-            std::memset(&b, 0, sizeof(b));
-            b.type = v.type;
-            b.mem = GX_MEM_DEVICE;
-            b.values = v.values;
-            b.nulls = v.has_nulls ? v.nulls : nullptr;
-            b.offsets = v.offsets;
-            b.data = v.bytes;
-        }
+        std::vector<gx_block> blocks;
+        for (size_t c = 0; c < probe_buf.cols.size(); c++)
+            blocks.push_back(view_block(probe_buf.view((int32_t)c)));
         gx_chunk ch{(int32_t)probe_buf.n_rows, (int32_t)blocks.size(),
                     blocks.data()};
         int rc = probe(&ch, out);
-        probe_buf.release();
+        probe_buf.clear(); /* batch consumed; the next push re-inits */
         probe_buf_init = false;
         return rc;
     }
@@ -1798,13 +1794,12 @@ struct JoinOp : gx_op {
         uint32_t cnt = 0;
         HIP_OK(hipMemcpyAsync(&cnt, d_cnt.p, 4, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
-        if (cnt == 0) { d_idx.release(); d_cnt.release(); return 0; }
+        if (cnt == 0) return 0;
 
         std::vector<int32_t> otypes = output_types();
-        HipResult *h = alloc_result_cols(otypes, cnt, device, stream);
-        if (!h) { d_idx.release(); d_cnt.release(); return -1; }
+        auto h = alloc_result_cols(otypes, cnt, device, stream);
+        if (!h) return -1;
         size_t col = 0;
-        int rc_col = 0;
         for (auto &spec : projected_specs()) {
             /* buildOuter tail: outer columns come from the BUILD store,
              * inner columns are null-filled (nextJoinNullRows:372-401) */
@@ -1814,9 +1809,12 @@ struct JoinOp : gx_op {
             if (null_fill) src.type = spec.type;
             if (spec.type == GX_SLICE) {
                 if (gather_slice_col(src, (const uint32_t *)d_idx.p,
-                                     (int)null_fill, cnt, h, col, d_scan_tmp,
-                                     stream))
-                    rc_col = -1;
+                                     (int)null_fill, cnt, h.get(), col,
+                                     d_scan_tmp, stream)) {
+                    /* earlier columns' gathers still write into h */
+                    (void)hipStreamSynchronize(stream);
+                    return -1;
+                }
                 col++;
                 continue;
             }
@@ -1826,10 +1824,9 @@ struct JoinOp : gx_op {
                                (int)null_fill);
             col++;
         }
+        /* d_idx is freed on return: drain the gathers that read it */
         HIP_OK(hipStreamSynchronize(stream));
-        d_idx.release(); d_cnt.release();
-        if (rc_col != 0) { free_result(h); return -1; }
-        *out = &h->res;
+        give_result(std::move(h), out);
         return 0;
     }
 };
@@ -1962,13 +1959,12 @@ int gxop_result_to_host(gx_result *res) {
         b.nulls = h->host.back().data();
         b.mem = GX_MEM_HOST;
     }
-    for (auto &db : h->bufs) db.release();
     h->bufs.clear();
     return 0;
 }
 
 void gxop_result_release(gx_result *res) {
-    if (res && res->opaque) free_result(static_cast<HipResult *>(res->opaque));
+    if (res) delete static_cast<HipResult *>(res->opaque);
 }
 
 int gxop_result_copy_col(const gx_result *res, int32_t col, void *dst_values,

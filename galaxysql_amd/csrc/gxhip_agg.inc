@@ -538,11 +538,14 @@ struct AggOp : gx_op {
     std::vector<int32_t> group_cols_, input_types;
     std::vector<gx_agg_spec> aggs;
 
-    DevStore keystore;         /* appended group-key columns (for emit) */
-    DevBuf d_packed, d_nullmask;  /* packed fast-path key records */
-    DevBuf d_slots, d_krow_of_gid, d_hashes, d_tiles, d_total, d_slotidx;
-    DevBuf d_records;          /* AoS per-group state records */
+    /* device buffers, last-allocated first (see DevBuf: destruction order
+     * and the pool); d_slots / d_records, d_hashes / d_slotidx and
+     * d_krow_of_gid / d_slot_of_gid share a size class */
     DevBuf d_slot_of_gid;      /* slot mode: record index per gid */
+    DevBuf d_records;          /* AoS per-group state records */
+    DevBuf d_slotidx, d_total, d_tiles, d_hashes, d_krow_of_gid, d_slots;
+    DevBuf d_nullmask, d_packed;  /* packed fast-path key records */
+    DevStore keystore;         /* appended group-key columns (for emit) */
     bool slot_records = false; /* records indexed by slot (stride <= 2) */
     int32_t stride = 0;        /* record size in u64s */
     int32_t val_off[GX_MAX_COLS] = {0};
@@ -616,11 +619,6 @@ struct AggOp : gx_op {
         slot_records = stride <= 2 && cfg.n_group_cols > 0;
     }
     ~AggOp() override {
-        keystore.release();
-        d_packed.release(); d_nullmask.release();
-        d_slots.release(); d_krow_of_gid.release(); d_hashes.release();
-        d_tiles.release(); d_total.release(); d_slotidx.release();
-        d_records.release(); d_slot_of_gid.release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
     }
@@ -708,15 +706,11 @@ struct AggOp : gx_op {
                                slot_records ? stride : 0,
                                (uint32_t *)d_slot_of_gid.p);
         }
+        /* the rehash kernel reads the old table: drain before move
+         * assignment returns it to the pool */
         HIP_OK(hipStreamSynchronize(stream));
-        d_slots.release();
-        d_slots = new_slots;
-        new_slots.p = nullptr;
-        if (slot_records) {
-            d_records.release();
-            d_records = new_records;
-            new_records.p = nullptr;
-        }
+        d_slots = std::move(new_slots);
+        if (slot_records) d_records = std::move(new_records);
         n_slots = ns;
         mask = (uint32_t)(ns - 1);
         return 0;
@@ -743,27 +737,15 @@ struct AggOp : gx_op {
         if (!no_group_by) {
             /* append key columns (for emit + generic compare) */
             std::vector<gx_block> kb;
-            for (int32_t gc : group_cols_) {
-                gx_block b{};
-                const DevColView &v = st.views[gc];
-                b.type = v.type;
-                b.mem = GX_MEM_DEVICE;
-                b.values = v.values;
-                b.nulls = v.has_nulls ? v.nulls : nullptr;
-                if (v.type == GX_SLICE) {
-                    b.offsets = v.offsets;
-                    b.data = v.bytes;
-                }
-                kb.push_back(b);
-            }
+            for (int32_t gc : group_cols_) kb.push_back(view_block(st.views[gc]));
             gx_chunk kc;
             kc.n_rows = (int32_t)n;
             kc.n_blocks = (int32_t)kb.size();
             kc.blocks = kb.data();
-            if (keystore.append(&kc)) { st.release(); return -1; }
+            if (keystore.append(&kc)) return -1;
 
             if (d_hashes.grow((size_t)n * 4, stream) ||
-                d_slotidx.grow((size_t)n * 4, stream)) { st.release(); return -1; }
+                d_slotidx.grow((size_t)n * 4, stream)) return -1;
             KeyViews chunk_keys;
             chunk_keys.n = (int32_t)group_cols_.size();
             for (size_t i = 0; i < group_cols_.size(); i++)
@@ -771,10 +753,8 @@ struct AggOp : gx_op {
 
             if (use_packed) {
                 if (d_packed.grow((size_t)(base_krow + n) * sizeof(PackedKey), stream) ||
-                    d_nullmask.grow((size_t)(base_krow + n), stream)) {
-                    st.release();
+                    d_nullmask.grow((size_t)(base_krow + n), stream))
                     return -1;
-                }
                 hipLaunchKernelGGL(k_agg_pack, dim3(gx_grid(n)), dim3(256), 0,
                                    stream, chunk_keys, n, base_krow,
                                    (PackedKey *)d_packed.p,
@@ -791,12 +771,12 @@ struct AggOp : gx_op {
             const bool small_chunk = n < (int64_t)(1 << 18);
             if (small_chunk) {
                 /* inline gids need capacity for the worst case up front */
-                if (ensure_table((int64_t)n_groups_host + n)) { st.release(); return -1; }
-                if (ensure_group_cap((int64_t)n_groups_host + n)) { st.release(); return -1; }
+                if (ensure_table((int64_t)n_groups_host + n)) return -1;
+                if (ensure_group_cap((int64_t)n_groups_host + n)) return -1;
             } else {
-                if (ensure_table((int64_t)n_groups_host + 1024)) { st.release(); return -1; }
+                if (ensure_table((int64_t)n_groups_host + 1024)) return -1;
             }
-            if (d_total.grow(12, stream)) { st.release(); return -1; }
+            if (d_total.grow(12, stream)) return -1;
             if (small_chunk)
                 /* once, BEFORE the overflow-retry loop: gids assigned in a
                  * partial attempt must not be reissued on the rerun */
@@ -834,8 +814,8 @@ struct AggOp : gx_op {
                                       hipMemcpyDeviceToHost, stream));
                 HIP_OK(hipStreamSynchronize(stream));
                 if (!ovf) break;
-                if (attempt > 40) { gx_set_err("agg table overflow loop"); st.release(); return -1; }
-                if (ensure_table(0, /*force_double=*/true)) { st.release(); return -1; }
+                if (attempt > 40) { gx_set_err("agg table overflow loop"); return -1; }
+                if (ensure_table(0, /*force_double=*/true)) return -1;
             }
 
             if (small_chunk) {
@@ -849,7 +829,7 @@ struct AggOp : gx_op {
             {
             /* dense gid compaction over the slot table (no hot counter) */
             int64_t n_tiles = (n_slots + GX_GID_TILE - 1) / GX_GID_TILE;
-            if (d_tiles.grow((size_t)n_tiles * 4, stream)) { st.release(); return -1; }
+            if (d_tiles.grow((size_t)n_tiles * 4, stream)) return -1;
             hipLaunchKernelGGL(k_agg_gid_count,
                                dim3((int)std::min<int64_t>(n_tiles, 4096)),
                                dim3(256), 0, stream,
@@ -863,7 +843,7 @@ struct AggOp : gx_op {
                                   hipMemcpyDeviceToHost, stream));
             HIP_OK(hipStreamSynchronize(stream));
             /* grow per-group state only now that the real count is known */
-            if (ensure_group_cap(total)) { st.release(); return -1; }
+            if (ensure_group_cap(total)) return -1;
             hipLaunchKernelGGL(k_agg_gid_assign,
                                dim3((int)std::min<int64_t>(n_tiles, 4096)),
                                dim3(256), 0, stream,
@@ -876,7 +856,7 @@ struct AggOp : gx_op {
         accumulate:;
         } else {
             if (!global_agg_seeded) {
-                if (ensure_group_cap(1)) { st.release(); return -1; }
+                if (ensure_group_cap(1)) return -1;
                 n_groups_host = 1;
                 global_agg_seeded = true;
             }
@@ -921,7 +901,6 @@ struct AggOp : gx_op {
             consumes++;
             rows_total += n;
         }
-        st.release();
         return 0;
     }
 
@@ -947,7 +926,7 @@ struct AggOp : gx_op {
                        sp.func == GX_AGG_MAX_F64 || sp.func == GX_AGG_AVG_F64;
             otypes.push_back(f64 ? GX_F64 : GX_I64);
         }
-        HipResult *h = alloc_result_cols(otypes, ng, device, stream);
+        auto h = alloc_result_cols(otypes, ng, device, stream);
         if (!h) return -1;
         if (ng > 0) {
             size_t col = 0;
@@ -955,11 +934,9 @@ struct AggOp : gx_op {
                 DevColView kv = keystore.view((int32_t)kc);
                 if (kv.type == GX_SLICE) {
                     if (gather_slice_col(kv, (const uint32_t *)d_krow_of_gid.p,
-                                         0, ng, h, col, d_tiles /* reuse */,
-                                         stream)) {
-                        free_result(h);
+                                         0, ng, h.get(), col,
+                                         d_tiles /* reuse */, stream))
                         return -1;
-                    }
                     col++;
                     continue;
                 }
@@ -983,7 +960,7 @@ struct AggOp : gx_op {
             }
             HIP_OK(hipStreamSynchronize(stream));
         }
-        *out = &h->res;
+        give_result(std::move(h), out);
         return 0;
     }
 };

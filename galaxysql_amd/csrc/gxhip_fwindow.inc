@@ -524,11 +524,12 @@ struct FWindowOp : gx_op {
     gx_fwindow_cfg cfg;
     std::vector<int32_t> part_cols_, order_cols_, input_types;
     std::vector<gx_frame_spec> frames;
+    /* last-allocated first (see DevBuf: destruction order and the pool) */
+    DevBuf d_nn2, d_dvals;            /* f64 value + non-null prefixes */
+    DevBuf d_span, d_fhi, d_flo;      /* RANGE frame per-row bounds */
+    DevBuf d_navidx, d_runstarts, d_runid, d_runheads;
+    DevBuf d_tmp, d_rec, d_vals, d_starts, d_cont, d_seg, d_heads;
     DevStore input;
-    DevBuf d_heads, d_seg, d_cont, d_starts, d_vals, d_rec, d_tmp;
-    DevBuf d_runheads, d_runid, d_runstarts, d_navidx;
-    DevBuf d_flo, d_fhi, d_span;      /* RANGE frame per-row bounds */
-    DevBuf d_dvals, d_nn2;            /* f64 value + non-null prefixes */
     bool finished = false, emitted = false;
     bool needs_runs = false;
     uint32_t n_segs = 0, n_runs = 0;
@@ -545,17 +546,6 @@ struct FWindowOp : gx_op {
                           fr.func == GX_AGG_PERCENT_RANK;
         input.init((int32_t)input_types.size(), input_types.data(), stream);
     }
-    ~FWindowOp() override {
-        input.release();
-        d_heads.release(); d_seg.release(); d_cont.release();
-        d_starts.release(); d_vals.release(); d_rec.release();
-        d_tmp.release();
-        d_runheads.release(); d_runid.release(); d_runstarts.release();
-        d_navidx.release();
-        d_flo.release(); d_fhi.release(); d_span.release();
-        d_dvals.release(); d_nn2.release();
-    }
-
     int consume(const gx_chunk *ch) {
         if (ensure_device(device)) return -1;
         return input.append(ch);
@@ -587,18 +577,10 @@ struct FWindowOp : gx_op {
         }
         hipLaunchKernelGGL(k_win_heads, dim3(gx_grid(n)), dim3(256), 0,
                            stream, H);
-        size_t tmp = 0;
-        HIP_OK(hipcub::DeviceScan::InclusiveSum(
-            nullptr, tmp, (uint32_t *)d_heads.p, (uint32_t *)d_seg.p, n,
-            stream));
-        if (d_tmp.grow(tmp, stream)) return -1;
-        HIP_OK(hipcub::DeviceScan::InclusiveSum(
-            d_tmp.p, tmp, (uint32_t *)d_heads.p, (uint32_t *)d_seg.p, n,
-            stream));
         uint32_t last = 0;
-        HIP_OK(hipMemcpyAsync(&last, (uint32_t *)d_seg.p + (n - 1), 4,
-                              hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipStreamSynchronize(stream));
+        if (cub_inclusive_sum_total(d_tmp, stream, (uint32_t *)d_heads.p,
+                                    (uint32_t *)d_seg.p, n, &last))
+            return -1;
         n_segs = last + 1;
         /* k_win_heads with no carry flags row 0 as a head, so the
          * InclusiveSum ids run 1..last; entry 0 of d_starts is simply
@@ -610,17 +592,10 @@ struct FWindowOp : gx_op {
                            (uint32_t *)d_starts.p);
         if (needs_runs) {
             if (d_runid.grow((size_t)n * 4, stream)) return -1;
-            HIP_OK(hipcub::DeviceScan::InclusiveSum(
-                nullptr, tmp, (uint32_t *)d_runheads.p,
-                (uint32_t *)d_runid.p, n, stream));
-            if (d_tmp.grow(tmp, stream)) return -1;
-            HIP_OK(hipcub::DeviceScan::InclusiveSum(
-                d_tmp.p, tmp, (uint32_t *)d_runheads.p,
-                (uint32_t *)d_runid.p, n, stream));
             uint32_t rlast = 0;
-            HIP_OK(hipMemcpyAsync(&rlast, (uint32_t *)d_runid.p + (n - 1), 4,
-                                  hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipStreamSynchronize(stream));
+            if (cub_inclusive_sum_total(d_tmp, stream, (uint32_t *)d_runheads.p,
+                                        (uint32_t *)d_runid.p, n, &rlast))
+                return -1;
             n_runs = rlast + 1;
             if (d_runstarts.grow((size_t)n_runs * 4, stream)) return -1;
             hipLaunchKernelGGL(k_fw_seg_starts, dim3(gx_grid(n)), dim3(256),
@@ -645,43 +620,33 @@ struct FWindowOp : gx_op {
         int32_t n_levels = 1;
         while (((int64_t)1 << n_levels) <= span && n_levels < 40) n_levels++;
         DevBuf d_levels, d_nn, d_nn_tmp;
-        int rc = -1;
-        do {
-            if (d_levels.grow((size_t)n_levels * n * sizeof(T), stream) ||
-                d_nn.grow((size_t)n * 8, stream))
-                break;
-            auto *lv = (T *)d_levels.p;
-            hipLaunchKernelGGL((k_fw_st_map<T>), dim3(gx_grid(n)), dim3(256),
-                               0, stream, in, n, identity, lv,
-                               (unsigned long long *)d_nn.p);
-            for (int32_t k = 1; k < n_levels; k++)
-                hipLaunchKernelGGL((k_fw_st_build<T, Op>), dim3(gx_grid(n)),
-                                   dim3(256), 0, stream,
-                                   lv + (size_t)(k - 1) * n, n,
-                                   (int64_t)1 << (k - 1),
-                                   lv + (size_t)k * n, op);
-            size_t tmp = 0;
-            bool bad = false;
-            if (hipcub::DeviceScan::InclusiveSum(
-                    nullptr, tmp, (unsigned long long *)d_nn.p,
-                    (unsigned long long *)d_nn.p, n, stream) != hipSuccess)
-                bad = true;
-            if (bad || d_nn_tmp.grow(tmp, stream)) break;
-            if (hipcub::DeviceScan::InclusiveSum(
-                    d_nn_tmp.p, tmp, (unsigned long long *)d_nn.p,
-                    (unsigned long long *)d_nn.p, n, stream) != hipSuccess)
-                break;
-            hipLaunchKernelGGL((k_fw_st_query<T, Op>), dim3(gx_grid(n)),
-                               dim3(256), 0, stream, lv, n, n_levels, seg,
-                               (const uint32_t *)d_starts.p, n_segs,
-                               fr.preceding, fr.following, lo_arr, hi_arr,
-                               (const unsigned long long *)d_nn.p, is_f64,
-                               op, h->bufs[col * 2].p,
-                               (uint8_t *)h->bufs[col * 2 + 1].p);
-            rc = 0;
-        } while (0);
-        d_levels.release(); d_nn.release(); d_nn_tmp.release();
-        return rc;
+        if (d_levels.grow((size_t)n_levels * n * sizeof(T), stream) ||
+            d_nn.grow((size_t)n * 8, stream))
+            return -1;
+        auto *lv = (T *)d_levels.p;
+        hipLaunchKernelGGL((k_fw_st_map<T>), dim3(gx_grid(n)), dim3(256),
+                           0, stream, in, n, identity, lv,
+                           (unsigned long long *)d_nn.p);
+        for (int32_t k = 1; k < n_levels; k++)
+            hipLaunchKernelGGL((k_fw_st_build<T, Op>), dim3(gx_grid(n)),
+                               dim3(256), 0, stream,
+                               lv + (size_t)(k - 1) * n, n,
+                               (int64_t)1 << (k - 1),
+                               lv + (size_t)k * n, op);
+        if (cub_run(d_nn_tmp, stream, [&](void *t, size_t &b) {
+                return hipcub::DeviceScan::InclusiveSum(
+                    t, b, (unsigned long long *)d_nn.p,
+                    (unsigned long long *)d_nn.p, n, stream);
+            }))
+            return -1;
+        hipLaunchKernelGGL((k_fw_st_query<T, Op>), dim3(gx_grid(n)),
+                           dim3(256), 0, stream, lv, n, n_levels, seg,
+                           (const uint32_t *)d_starts.p, n_segs,
+                           fr.preceding, fr.following, lo_arr, hi_arr,
+                           (const unsigned long long *)d_nn.p, is_f64,
+                           op, h->bufs[col * 2].p,
+                           (uint8_t *)h->bufs[col * 2 + 1].p);
+        return 0;
     }
 
     int next(gx_result **out) {
@@ -708,39 +673,17 @@ struct FWindowOp : gx_op {
             default: otypes.push_back(GX_F64); break;
             }
         }
-        HipResult *h = alloc_result_cols(otypes, n, device, stream);
+        auto h = alloc_result_cols(otypes, n, device, stream);
         if (!h) return -1;
-        bool fail = false;
-        /* pass-through input columns */
-        for (size_t c = 0; c < input_types.size() && !fail; c++) {
-            DevColView v = input.view((int32_t)c);
-            if (input_types[c] == GX_SLICE) {
-                DevBuf iota;
-                if (iota.grow((size_t)n * 4, stream)) { fail = true; break; }
-                hipLaunchKernelGGL(k_iota, dim3(gx_grid(n)), dim3(256), 0,
-                                   stream, (uint32_t *)iota.p, n);
-                if (gather_slice_col(v, (const uint32_t *)iota.p, 0, n, h, c,
-                                     d_tmp, stream))
-                    fail = true;
-                iota.release();
-                continue;
-            }
-            size_t es = gx_fixed_size(input_types[c]);
-            HIP_OK_BRK(hipMemcpyAsync(h->bufs[c * 2].p, v.values,
-                                      (size_t)n * es, hipMemcpyDeviceToDevice,
-                                      stream));
-            if (v.nulls)
-                HIP_OK_BRK(hipMemcpyAsync(h->bufs[c * 2 + 1].p, v.nulls,
-                                          (size_t)n, hipMemcpyDeviceToDevice,
-                                          stream));
-            else
-                HIP_OK_BRK(hipMemsetAsync(h->bufs[c * 2 + 1].p, 0, (size_t)n,
-                                          stream));
-        }
-        if (fail) { free_result(h); return -1; }
+        std::vector<DevColView> in_views;
+        for (size_t c = 0; c < input_types.size(); c++)
+            in_views.push_back(input.view((int32_t)c));
+        if (copy_input_cols(input_types, in_views.data(), n, h.get(), d_tmp,
+                            stream))
+            return -1;
 
         const uint32_t *seg = (const uint32_t *)d_seg.p;
-        for (size_t a = 0; a < frames.size() && !fail; a++) {
+        for (size_t a = 0; a < frames.size(); a++) {
             const gx_frame_spec &f = frames[a];
             size_t col = input_types.size() + a;
             DevColView in{};
@@ -765,7 +708,7 @@ struct FWindowOp : gx_op {
                 continue;
             }
             if (f.func >= GX_AGG_FIRST_VALUE && f.func <= GX_AGG_LEAD) {
-                if (d_navidx.grow((size_t)n * 4, stream)) { fail = true; break; }
+                if (d_navidx.grow((size_t)n * 4, stream)) return -1;
                 hipLaunchKernelGGL(k_fw_navigate, dim3(gx_grid(n)), dim3(256),
                                    0, stream, seg,
                                    (const uint32_t *)d_starts.p, n_segs, n,
@@ -773,10 +716,8 @@ struct FWindowOp : gx_op {
                                    (uint32_t *)d_navidx.p);
                 if (in.type == GX_SLICE) {
                     if (gather_slice_col(in, (const uint32_t *)d_navidx.p, 0,
-                                         n, h, col, d_tmp, stream)) {
-                        fail = true;
-                        break;
-                    }
+                                         n, h.get(), col, d_tmp, stream))
+                        return -1;
                 } else {
                     hipLaunchKernelGGL(k_gather, dim3(gx_grid(n)), dim3(256),
                                        0, stream, in,
@@ -805,10 +746,7 @@ struct FWindowOp : gx_op {
                 case GX_AGG_BIT_AND: tmpl0 = ~0ull; break;
                 default: tmpl0 = 0ull; break;
                 }
-                if (d_rec.grow((size_t)n_segs * stride * 8, stream)) {
-                    fail = true;
-                    break;
-                }
+                if (d_rec.grow((size_t)n_segs * stride * 8, stream)) return -1;
                 AggInitParams IP;
                 IP.records = (unsigned long long *)d_rec.p;
                 IP.stride = stride;
@@ -852,9 +790,8 @@ struct FWindowOp : gx_op {
                 if (is_range) {
                     if (d_flo.grow((size_t)n * 4, stream) ||
                         d_fhi.grow((size_t)n * 4, stream) ||
-                        d_span.grow(4, stream)) { fail = true; break; }
-                    HIP_OK_BRK(hipMemsetAsync(d_span.p, 0, 4, stream));
-                    if (fail) break;
+                        d_span.grow(4, stream)) return -1;
+                    HIP_OK(hipMemsetAsync(d_span.p, 0, 4, stream));
                     hipLaunchKernelGGL(k_fw_range_bounds, dim3(gx_grid(n)),
                                        dim3(256), 0, stream,
                                        input.view(f.order_col), f.order_asc,
@@ -867,12 +804,10 @@ struct FWindowOp : gx_op {
                     d_hi_p = (const int32_t *)d_fhi.p;
                     if (minmax) {
                         uint32_t sp = 0;
-                        HIP_OK_BRK(hipMemcpyAsync(&sp, d_span.p, 4,
-                                                  hipMemcpyDeviceToHost,
-                                                  stream));
-                        if (fail) break;
-                        HIP_OK_BRK(hipStreamSynchronize(stream));
-                        if (fail) break;
+                        HIP_OK(hipMemcpyAsync(&sp, d_span.p, 4,
+                                              hipMemcpyDeviceToHost,
+                                              stream));
+                        HIP_OK(hipStreamSynchronize(stream));
                         range_span = sp;
                     }
                 }
@@ -881,53 +816,37 @@ struct FWindowOp : gx_op {
                     switch (f.func) {
                     case GX_AGG_MIN_I64:
                         r = run_minmax<long long>(f, in, n, seg, INT64_MAX,
-                                                  StMinI64(), 0, h, col,
+                                                  StMinI64(), 0, h.get(), col,
                                                   d_lo_p, d_hi_p, range_span);
                         break;
                     case GX_AGG_MAX_I64:
                         r = run_minmax<long long>(f, in, n, seg, INT64_MIN,
-                                                  StMaxI64(), 0, h, col,
+                                                  StMaxI64(), 0, h.get(), col,
                                                   d_lo_p, d_hi_p, range_span);
                         break;
                     case GX_AGG_MIN_F64:
                         r = run_minmax<double>(f, in, n, seg, INFINITY,
-                                               StMinF64(), 1, h, col,
+                                               StMinF64(), 1, h.get(), col,
                                                d_lo_p, d_hi_p, range_span);
                         break;
                     default:
                         r = run_minmax<double>(f, in, n, seg, -INFINITY,
-                                               StMaxF64(), 1, h, col,
+                                               StMaxF64(), 1, h.get(), col,
                                                d_lo_p, d_hi_p, range_span);
                         break;
                     }
-                    if (r) { fail = true; break; }
+                    if (r) return -1;
                 } else if (is_f64sum) {
                     /* SUM_F64/AVG_F64: double prefix + non-null prefix */
                     if (d_dvals.grow((size_t)n * 8, stream) ||
-                        d_nn2.grow((size_t)n * 8, stream)) { fail = true; break; }
+                        d_nn2.grow((size_t)n * 8, stream)) return -1;
                     auto *dv = (double *)d_dvals.p;
                     auto *nn = (unsigned long long *)d_nn2.p;
                     hipLaunchKernelGGL(k_fw_map_f64, dim3(gx_grid(n)),
                                        dim3(256), 0, stream, in, n, dv, nn);
-                    size_t tmp = 0;
-                    HIP_OK_BRK(hipcub::DeviceScan::InclusiveScanByKey(
-                        nullptr, tmp, seg, dv, dv, FwSumF64(), n,
-                        hipcub::Equality(), stream));
-                    if (fail) break;
-                    if (d_tmp.grow(tmp, stream)) { fail = true; break; }
-                    HIP_OK_BRK(hipcub::DeviceScan::InclusiveScanByKey(
-                        d_tmp.p, tmp, seg, dv, dv, FwSumF64(), n,
-                        hipcub::Equality(), stream));
-                    if (fail) break;
-                    HIP_OK_BRK(hipcub::DeviceScan::InclusiveScanByKey(
-                        nullptr, tmp, seg, nn, nn, WinSumU64(), n,
-                        hipcub::Equality(), stream));
-                    if (fail) break;
-                    if (d_tmp.grow(tmp, stream)) { fail = true; break; }
-                    HIP_OK_BRK(hipcub::DeviceScan::InclusiveScanByKey(
-                        d_tmp.p, tmp, seg, nn, nn, WinSumU64(), n,
-                        hipcub::Equality(), stream));
-                    if (fail) break;
+                    if (seg_scan(d_tmp, stream, seg, dv, n, FwSumF64()) ||
+                        seg_scan(d_tmp, stream, seg, nn, n, WinSumU64()))
+                        return -1;
                     hipLaunchKernelGGL(k_fw_diff_f64, dim3(gx_grid(n)),
                                        dim3(256), 0, stream, in, dv, nn, seg,
                                        (const uint32_t *)d_starts.p, n_segs,
@@ -942,37 +861,22 @@ struct FWindowOp : gx_op {
                     /* additive funcs: segmented prefix + differences;
                      * SUM_I64N (null-init Sum) adds a non-null-count
                      * prefix so empty/all-null frames emit NULL */
-                    if (d_vals.grow((size_t)n * 8, stream)) { fail = true; break; }
+                    if (d_vals.grow((size_t)n * 8, stream)) return -1;
                     auto *vals = (unsigned long long *)d_vals.p;
                     hipLaunchKernelGGL(k_win_map_u64, dim3(gx_grid(n)),
                                        dim3(256), 0, stream, in, f.func, n,
                                        vals);
-                    size_t tmp = 0;
-                    HIP_OK_BRK(hipcub::DeviceScan::InclusiveScanByKey(
-                        nullptr, tmp, seg, vals, vals, WinSumU64(), n,
-                        hipcub::Equality(), stream));
-                    if (fail) break;
-                    if (d_tmp.grow(tmp, stream)) { fail = true; break; }
-                    HIP_OK_BRK(hipcub::DeviceScan::InclusiveScanByKey(
-                        d_tmp.p, tmp, seg, vals, vals, WinSumU64(), n,
-                        hipcub::Equality(), stream));
-                    if (fail) break;
+                    if (seg_scan(d_tmp, stream, seg, vals, n, WinSumU64()))
+                        return -1;
                     const unsigned long long *nnp = nullptr;
                     if (f.func == GX_AGG_SUM_I64N) {
-                        if (d_nn2.grow((size_t)n * 8, stream)) { fail = true; break; }
+                        if (d_nn2.grow((size_t)n * 8, stream)) return -1;
                         auto *nn = (unsigned long long *)d_nn2.p;
                         hipLaunchKernelGGL(k_win_map_u64, dim3(gx_grid(n)),
                                            dim3(256), 0, stream, in,
                                            (int32_t)GX_AGG_COUNT_COL, n, nn);
-                        HIP_OK_BRK(hipcub::DeviceScan::InclusiveScanByKey(
-                            nullptr, tmp, seg, nn, nn, WinSumU64(), n,
-                            hipcub::Equality(), stream));
-                        if (fail) break;
-                        if (d_tmp.grow(tmp, stream)) { fail = true; break; }
-                        HIP_OK_BRK(hipcub::DeviceScan::InclusiveScanByKey(
-                            d_tmp.p, tmp, seg, nn, nn, WinSumU64(), n,
-                            hipcub::Equality(), stream));
-                        if (fail) break;
+                        if (seg_scan(d_tmp, stream, seg, nn, n, WinSumU64()))
+                            return -1;
                         nnp = nn;
                     }
                     hipLaunchKernelGGL(k_fw_prefix_diff, dim3(gx_grid(n)),
@@ -987,9 +891,8 @@ struct FWindowOp : gx_op {
                 }
             }
         }
-        if (fail) { free_result(h); return -1; }
         HIP_OK(hipStreamSynchronize(stream));
-        *out = &h->res;
+        give_result(std::move(h), out);
         return 0;
     }
 };

@@ -230,8 +230,10 @@ struct GroupJoinOp : gx_op {
     std::vector<int32_t> build_types, probe_types, group_cols_;
     std::vector<gx_agg_spec> aggs;
 
-    JoinOp *jop = nullptr;       /* CSR build (null-safe hashing) */
-    DevBuf d_records, d_used, d_gidx, d_cnt, d_gj_tmp, d_ph, d_pn;
+    /* last-allocated first (see DevBuf: destruction order and the pool) */
+    DevBuf d_wide;
+    DevBuf d_pn, d_ph, d_gj_tmp, d_cnt, d_gidx, d_used, d_records;
+    std::unique_ptr<JoinOp> jop; /* CSR build (null-safe hashing) */
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double kernel_ms = 0.0;
     int64_t rows_total = 0;
@@ -242,7 +244,6 @@ struct GroupJoinOp : gx_op {
     bool built = false, emitted = false;
     bool wide_ok = false;    /* cfg allows wide mode */
     bool wide = false;       /* chosen at do_build (needs null-free keys) */
-    DevBuf d_wide;
 
     GroupJoinOp(const gx_groupjoin_cfg *c)
         : gx_op(OP_GROUPJOIN, c->device, c->stream), cfg(*c) {
@@ -270,7 +271,7 @@ struct GroupJoinOp : gx_op {
         jc.device = device;
         jc.stream = (uint64_t)stream;
         jc.expected_build_rows = c->expected_build_rows;
-        jop = new JoinOp(&jc);
+        jop.reset(new JoinOp(&jc));
         jop->null_safe_keys = true;
 
         /* AoS record layout (same scheme as AggOp) */
@@ -311,10 +312,6 @@ struct GroupJoinOp : gx_op {
     std::vector<gx_equi_key> swapped_keys;
 
     ~GroupJoinOp() override {
-        delete jop;
-        d_records.release(); d_used.release(); d_gidx.release();
-        d_cnt.release(); d_gj_tmp.release(); d_ph.release(); d_pn.release();
-        d_wide.release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
     }
@@ -361,45 +358,35 @@ struct GroupJoinOp : gx_op {
         StagedChunk st;
         if (st.stage(ch, stream)) return -1;
         const int64_t n = st.n_rows;
-        int rc = -1;
-        do {
-            if (d_ph.grow((size_t)n * 4, stream) ||
-                d_pn.grow((size_t)n, stream)) break;
-            KeyViews pk = jop->key_views_staged(st, jop->probe_key_cols);
-            hipLaunchKernelGGL(k_hash_rows, dim3(gx_grid(n)), dim3(256), 0,
-                               stream, pk, n, (int32_t *)d_ph.p,
-                               (uint8_t *)d_pn.p, 1 /* null_safe */);
-            if (wide) {
-                GJWideProbeParams W;
-                std::memset(&W, 0, sizeof(W));
-                W.starts = (const uint32_t *)jop->d_starts.p;
-                W.wide = (GJWideEntry *)d_wide.p;
-                W.mask = jop->mask;
-                W.n = n;
-                W.hashes = (const int32_t *)d_ph.p;
-                W.probe_key = pk.col[0];
-                W.n_aggs = (int32_t)aggs.size();
-                for (size_t a = 0; a < aggs.size(); a++) {
-                    W.func[a] = aggs[a].func;
-                    if (aggs[a].input_col >= 0)
-                        W.input[a] = st.views[aggs[a].input_col];
-                }
-                if (!ev0) {
-                    HIP_OK(hipEventCreate(&ev0));
-                    HIP_OK(hipEventCreate(&ev1));
-                }
-                HIP_OK(hipEventRecord(ev0, stream));
-                hipLaunchKernelGGL(k_gjw_probe, dim3(gx_grid(n)), dim3(256),
-                                   0, stream, W);
-                HIP_OK(hipEventRecord(ev1, stream));
-                HIP_OK(hipStreamSynchronize(stream));
-                float ms = 0;
-                HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-                kernel_ms += ms;
-                rows_total += n;
-                rc = 0;
-                break;
+        if (d_ph.grow((size_t)n * 4, stream) ||
+            d_pn.grow((size_t)n, stream)) return -1;
+        KeyViews pk = jop->key_views_staged(st, jop->probe_key_cols);
+        hipLaunchKernelGGL(k_hash_rows, dim3(gx_grid(n)), dim3(256), 0,
+                           stream, pk, n, (int32_t *)d_ph.p,
+                           (uint8_t *)d_pn.p, 1 /* null_safe */);
+        if (!ev0) {
+            HIP_OK(hipEventCreate(&ev0));
+            HIP_OK(hipEventCreate(&ev1));
+        }
+        if (wide) {
+            GJWideProbeParams W;
+            std::memset(&W, 0, sizeof(W));
+            W.starts = (const uint32_t *)jop->d_starts.p;
+            W.wide = (GJWideEntry *)d_wide.p;
+            W.mask = jop->mask;
+            W.n = n;
+            W.hashes = (const int32_t *)d_ph.p;
+            W.probe_key = pk.col[0];
+            W.n_aggs = (int32_t)aggs.size();
+            for (size_t a = 0; a < aggs.size(); a++) {
+                W.func[a] = aggs[a].func;
+                if (aggs[a].input_col >= 0)
+                    W.input[a] = st.views[aggs[a].input_col];
             }
+            HIP_OK(hipEventRecord(ev0, stream));
+            hipLaunchKernelGGL(k_gjw_probe, dim3(gx_grid(n)), dim3(256),
+                               0, stream, W);
+        } else {
             GJProbeParams P;
             std::memset(&P, 0, sizeof(P));
             P.starts = (const uint32_t *)jop->d_starts.p;
@@ -421,25 +408,18 @@ struct GroupJoinOp : gx_op {
                     P.A.input[a] = st.views[aggs[a].input_col];
             }
             P.A.records = (unsigned long long *)d_records.p;
-            if (!ev0) {
-                HIP_OK(hipEventCreate(&ev0));
-                HIP_OK(hipEventCreate(&ev1));
-            }
             HIP_OK(hipEventRecord(ev0, stream));
             hipLaunchKernelGGL(k_gj_probe, dim3(gx_grid(n)), dim3(256), 0,
                                stream, P);
-            HIP_OK(hipEventRecord(ev1, stream));
-            HIP_OK(hipStreamSynchronize(stream));
-            {
-                float ms = 0;
-                HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-                kernel_ms += ms;
-                rows_total += n;
-            }
-            rc = 0;
-        } while (0);
-        st.release();
-        return rc;
+        }
+        HIP_OK(hipEventRecord(ev1, stream));
+        /* also drains the probe before the staged chunk is freed */
+        HIP_OK(hipStreamSynchronize(stream));
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
+        kernel_ms += ms;
+        rows_total += n;
+        return 0;
     }
 
     int next(gx_result **out) {
@@ -489,12 +469,12 @@ struct GroupJoinOp : gx_op {
             default: otypes.push_back(GX_F64); break;
             }
         }
-        HipResult *h = alloc_result_cols(otypes, n_emit, device, stream);
+        auto h = alloc_result_cols(otypes, n_emit, device, stream);
         if (!h) return -1;
         /* LEFT emits in position order: materialize an identity index for
          * the gathers */
         if (emit_all) {
-            if (d_gidx.grow((size_t)n_build * 4, stream)) { free_result(h); return -1; }
+            if (d_gidx.grow((size_t)n_build * 4, stream)) return -1;
             hipLaunchKernelGGL(k_iota, dim3(gx_grid(n_build)), dim3(256), 0,
                                stream, (uint32_t *)d_gidx.p, n_build);
             idx = (const uint32_t *)d_gidx.p;
@@ -503,11 +483,9 @@ struct GroupJoinOp : gx_op {
         for (int32_t gc : group_cols_) {
             DevColView src = jop->build.view(gc);
             if (src.type == GX_SLICE) {
-                if (gather_slice_col(src, idx, 0, n_emit, h, col, d_gj_tmp,
-                                     stream)) {
-                    free_result(h);
+                if (gather_slice_col(src, idx, 0, n_emit, h.get(), col,
+                                     d_gj_tmp, stream))
                     return -1;
-                }
             } else {
                 hipLaunchKernelGGL(k_gather, dim3(gx_grid(n_emit)), dim3(256),
                                    0, stream, src, idx, n_emit,
@@ -527,7 +505,7 @@ struct GroupJoinOp : gx_op {
             col++;
         }
         HIP_OK(hipStreamSynchronize(stream));
-        *out = &h->res;
+        give_result(std::move(h), out);
         return 0;
     }
 };

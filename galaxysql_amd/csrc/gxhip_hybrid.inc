@@ -130,7 +130,7 @@ struct HybridJoinOp : gx_op {
     std::vector<int32_t> build_key_cols, probe_key_cols;
     int32_t P;
 
-    PartOp *build_router = nullptr, *probe_router = nullptr;
+    std::unique_ptr<PartOp> build_router, probe_router;
     std::vector<HostStore> build_parts, probe_parts;
 
     bool built = false, pass_nothing = false;
@@ -181,26 +181,24 @@ struct HybridJoinOp : gx_op {
         pc.input_types = bt.data();
         pc.device = device;
         pc.stream = (uint64_t)stream;
-        build_router = new PartOp(&pc);
+        build_router.reset(new PartOp(&pc));
         pc.n_key_cols = (int32_t)probe_key_cols.size();
         pc.key_cols = probe_key_cols.data();
         pc.n_input_cols = (int32_t)pt.size();
         pc.input_types = pt.data();
-        probe_router = new PartOp(&pc);
+        probe_router.reset(new PartOp(&pc));
     }
     ~HybridJoinOp() override {
-        delete build_router;
-        delete probe_router;
         for (auto *r : pending) gxop_result_release(r);
     }
 
     /* route one incoming chunk to the host partition stores of `side` */
-    int spill(PartOp *router, std::vector<HostStore> &parts,
+    int spill(PartOp &router, std::vector<HostStore> &parts,
               const gx_chunk *ch) {
         if (ch->n_rows == 0) return 0;
         gx_result *cat = nullptr;
         std::vector<int64_t> counts((size_t)P);
-        if (router->consume_concat(ch, &cat, counts.data())) return -1;
+        if (router.consume_concat(ch, &cat, counts.data())) return -1;
         if (!cat) return 0;
         if (gxop_result_to_host(cat)) {
             gxop_result_release(cat);
@@ -217,7 +215,7 @@ struct HybridJoinOp : gx_op {
 
     int consume(const gx_chunk *ch) {
         if (ensure_device(device)) return -1;
-        return spill(build_router, build_parts, ch);
+        return spill(*build_router, build_parts, ch);
     }
 
     int do_build() {
@@ -238,10 +236,40 @@ struct HybridJoinOp : gx_op {
         *out = nullptr;
         if (!built) { gx_set_err("probe before build"); return -1; }
         if (ensure_device(device)) return -1;
-        return spill(probe_router, probe_parts, ch);
+        return spill(*probe_router, probe_parts, ch);
     }
 
     static const int64_t PROBE_SUB = 16 << 20; /* rows per inner probe call */
+
+    /* queue a partition-join result for tail(); empty ones are dropped */
+    void keep(gx_result *res) {
+        if (res && res->chunk.n_rows > 0) pending.push_back(res);
+        else gxop_result_release(res);
+    }
+
+    /* build, probe and tail one partition's in-HBM join */
+    int join_partition(JoinOp &op, const HostStore &bs, const HostStore &ps) {
+        std::vector<gx_block> blk;
+        std::vector<std::vector<int32_t>> offs;
+        if (bs.n_rows > 0) {
+            gx_chunk bc = bs.slice_chunk(blk, offs, 0, bs.n_rows);
+            if (op.consume(&bc)) return -1;
+        }
+        if (op.do_build()) return -1;
+        for (int64_t r0 = 0; r0 < ps.n_rows; r0 += PROBE_SUB) {
+            int64_t r1 = std::min(ps.n_rows, r0 + PROBE_SUB);
+            gx_chunk pc = ps.slice_chunk(blk, offs, r0, r1);
+            gx_result *res = nullptr;
+            if (op.probe(&pc, &res)) return -1;
+            keep(res);
+        }
+        for (;;) {
+            gx_result *res = nullptr;
+            if (op.tail(&res)) return -1;
+            if (!res) return 0;
+            keep(res);
+        }
+    }
 
     int process_partition(int32_t p) {
         HostStore &bs = build_parts[(size_t)p];
@@ -265,43 +293,14 @@ struct HybridJoinOp : gx_op {
         c2.n_out_proj = (int32_t)out_proj.size();
         c2.n_conds = (int32_t)conds.size();
         c2.conds = conds.empty() ? nullptr : conds.data();
-        JoinOp *op = new JoinOp(&c2);
-        int rc = -1;
-        do {
-            std::vector<gx_block> blk;
-            std::vector<std::vector<int32_t>> offs;
-            if (bs.n_rows > 0) {
-                gx_chunk bc = bs.slice_chunk(blk, offs, 0, bs.n_rows);
-                if (op->consume(&bc)) break;
-            }
-            if (op->do_build()) break;
-            bool fail = false;
-            for (int64_t r0 = 0; r0 < ps.n_rows && !fail; r0 += PROBE_SUB) {
-                int64_t r1 = std::min(ps.n_rows, r0 + PROBE_SUB);
-                gx_chunk pc = ps.slice_chunk(blk, offs, r0, r1);
-                gx_result *res = nullptr;
-                if (op->probe(&pc, &res)) { fail = true; break; }
-                if (res) {
-                    if (res->chunk.n_rows > 0) pending.push_back(res);
-                    else gxop_result_release(res);
-                }
-            }
-            if (fail) break;
-            for (;;) {
-                gx_result *res = nullptr;
-                if (op->tail(&res)) { fail = true; break; }
-                if (!res) break;
-                if (res->chunk.n_rows > 0) pending.push_back(res);
-                else gxop_result_release(res);
-            }
-            if (fail) break;
-            rc = 0;
-        } while (0);
-        probe_kernel_ms += op->probe_kernel_ms;
-        probe_launches += op->probe_launches;
-        probe_rows_total += op->probe_rows_total;
-        matches_total += op->matches_total;
-        delete op;
+        /* the partition's device memory goes back to the pool when op
+         * leaves scope, before the next partition is built */
+        JoinOp op(&c2);
+        int rc = join_partition(op, bs, ps);
+        probe_kernel_ms += op.probe_kernel_ms;
+        probe_launches += op.probe_launches;
+        probe_rows_total += op.probe_rows_total;
+        matches_total += op.matches_total;
         /* free the partition's host staging eagerly */
         bs = HostStore();
         ps = HostStore();

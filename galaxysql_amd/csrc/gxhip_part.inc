@@ -82,6 +82,23 @@ struct PartOp : gx_op {
         return 0;
     }
 
+    /* gather rows idx[0..cnt) of every input column into result h */
+    int gather_rows(const StagedChunk &st, const uint32_t *idx, int64_t cnt,
+                    HipResult *h) {
+        for (size_t c = 0; c < input_types.size(); c++) {
+            if (input_types[c] == GX_SLICE) {
+                if (gather_slice_col(st.views[c], idx, 0, cnt, h, c, d_scan_tmp,
+                                     stream))
+                    return -1;
+                continue;
+            }
+            hipLaunchKernelGGL(k_gather, dim3(gx_grid(cnt)), dim3(256), 0, stream,
+                               st.views[c], idx, cnt, h->bufs[c * 2].p,
+                               (uint8_t *)h->bufs[c * 2 + 1].p, 0);
+        }
+        return 0;
+    }
+
     int consume(const gx_chunk *ch, gx_result **outs) {
         if (ensure_device(device)) return -1;
         const int64_t n = ch->n_rows;
@@ -92,45 +109,25 @@ struct PartOp : gx_op {
 
         StagedChunk st;
         if (st.stage(ch, stream)) return -1;
-        int rc = -1;
         DevBuf d_ids, d_counts, d_idx;
         std::vector<uint32_t> starts;
-        do {
-            if (route(st, n, d_ids, d_counts, d_idx, starts)) break;
-            bool ok = true;
-            for (int32_t p = 0; p < P && ok; p++) {
-                uint32_t cnt = starts[p + 1] - starts[p];
-                if (cnt == 0) continue;
-                HipResult *h = alloc_result_cols(input_types, cnt, device, stream);
-                if (!h) { ok = false; break; }
-                bool colfail = false;
-                for (size_t c = 0; c < input_types.size(); c++) {
-                    if (input_types[c] == GX_SLICE) {
-                        if (gather_slice_col(st.views[c],
-                                             (const uint32_t *)d_idx.p + starts[p],
-                                             0, cnt, h, c, d_scan_tmp, stream))
-                            colfail = true;
-                        continue;
-                    }
-                    hipLaunchKernelGGL(k_gather, dim3(gx_grid(cnt)), dim3(256), 0,
-                                       stream, st.views[c],
-                                       (const uint32_t *)d_idx.p + starts[p],
-                                       (int64_t)cnt, h->bufs[c * 2].p,
-                                       (uint8_t *)h->bufs[c * 2 + 1].p, 0);
-                }
-                if (colfail) { free_result(h); ok = false; break; }
-                outs[p] = &h->res;
-            }
-            if (!ok) break;
-            HIP_OK(hipStreamSynchronize(stream));
-            rc = 0;
-        } while (0);
-        d_ids.release(); d_counts.release(); d_idx.release();
-        st.release();
-        if (rc != 0)
-            for (int32_t p = 0; p < P; p++)
-                if (outs[p]) { gxop_result_release(outs[p]); outs[p] = nullptr; }
-        return rc;
+        if (route(st, n, d_ids, d_counts, d_idx, starts)) return -1;
+        /* held here until every partition succeeded: a failure frees them all */
+        std::vector<std::unique_ptr<HipResult>> res((size_t)P);
+        for (int32_t p = 0; p < P; p++) {
+            uint32_t cnt = starts[p + 1] - starts[p];
+            if (cnt == 0) continue;
+            res[p] = alloc_result_cols(input_types, cnt, device, stream);
+            if (!res[p]) return -1;
+            if (gather_rows(st, (const uint32_t *)d_idx.p + starts[p], cnt,
+                            res[p].get()))
+                return -1;
+        }
+        /* the staged chunk and d_idx are freed on return: drain first */
+        HIP_OK(hipStreamSynchronize(stream));
+        for (int32_t p = 0; p < P; p++)
+            if (res[p]) give_result(std::move(res[p]), &outs[p]);
+        return 0;
     }
 
     int consume_concat(const gx_chunk *ch, gx_result **out, int64_t *counts) {
@@ -139,46 +136,25 @@ struct PartOp : gx_op {
         const int64_t n = ch->n_rows;
         const int32_t P = cfg.n_parts;
         for (int32_t p = 0; p < P; p++) counts[p] = 0;
-        HipResult *h = nullptr;
         if (n == 0) {
-            h = alloc_result_cols(input_types, 0, device, stream);
+            auto h = alloc_result_cols(input_types, 0, device, stream);
             if (!h) return -1;
-            *out = &h->res;
+            give_result(std::move(h), out);
             return 0;
         }
         StagedChunk st;
         if (st.stage(ch, stream)) return -1;
-        int rc = -1;
         DevBuf d_ids, d_counts, d_idx;
         std::vector<uint32_t> starts;
-        do {
-            if (route(st, n, d_ids, d_counts, d_idx, starts)) break;
-            h = alloc_result_cols(input_types, n, device, stream);
-            if (!h) break;
-            bool colfail = false;
-            for (size_t c = 0; c < input_types.size(); c++) {
-                if (input_types[c] == GX_SLICE) {
-                    if (gather_slice_col(st.views[c], (const uint32_t *)d_idx.p,
-                                         0, n, h, c, d_scan_tmp, stream))
-                        colfail = true;
-                    continue;
-                }
-                hipLaunchKernelGGL(k_gather, dim3(gx_grid(n)), dim3(256), 0, stream,
-                                   st.views[c], (const uint32_t *)d_idx.p, n,
-                                   h->bufs[c * 2].p,
-                                   (uint8_t *)h->bufs[c * 2 + 1].p, 0);
-            }
-            if (colfail) break;
-            HIP_OK(hipStreamSynchronize(stream));
-            for (int32_t p = 0; p < P; p++) counts[p] = starts[p + 1] - starts[p];
-            *out = &h->res;
-            h = nullptr;
-            rc = 0;
-        } while (0);
-        d_ids.release(); d_counts.release(); d_idx.release();
-        st.release();
-        if (h) free_result(h);
-        return rc;
+        if (route(st, n, d_ids, d_counts, d_idx, starts)) return -1;
+        auto h = alloc_result_cols(input_types, n, device, stream);
+        if (!h) return -1;
+        if (gather_rows(st, (const uint32_t *)d_idx.p, n, h.get())) return -1;
+        /* the staged chunk and d_idx are freed on return: drain first */
+        HIP_OK(hipStreamSynchronize(stream));
+        for (int32_t p = 0; p < P; p++) counts[p] = starts[p + 1] - starts[p];
+        give_result(std::move(h), out);
+        return 0;
     }
 };
 

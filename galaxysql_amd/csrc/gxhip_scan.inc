@@ -273,8 +273,9 @@ struct ScanOp : gx_op {
     std::vector<gx_pred> preds;
     std::vector<gx_proj> projs;
     std::vector<int32_t> input_types, out_types;
-    DevBuf d_meta, d_rowids, d_scan_tmp;
+    /* last-allocated first (see DevBuf: destruction order and the pool) */
     std::vector<DevBuf> d_pats;
+    DevBuf d_scan_tmp, d_rowids, d_meta;
     bool has_slice_out = false;
 
     ScanOp(const gx_scan_cfg *c) : gx_op(OP_SCAN, c->device, c->stream), cfg(*c) {
@@ -290,12 +291,6 @@ struct ScanOp : gx_op {
             }
             if (out_types.back() == GX_SLICE) has_slice_out = true;
         }
-    }
-    ~ScanOp() override {
-        d_meta.release();
-        d_rowids.release();
-        d_scan_tmp.release();
-        for (auto &b : d_pats) b.release();
     }
 
     int upload_patterns() {
@@ -318,90 +313,80 @@ struct ScanOp : gx_op {
         const int64_t n = ch->n_rows;
         StagedChunk st;
         if (st.stage(ch, stream)) return -1;
-        int rc = -1;
-        do {
-            if (d_meta.grow(8, stream)) break;
-            /* pass 1 would count; instead allocate full-capacity output and
-             * shrink by the counter (filters keep a bounded fraction and
-             * the buffers come from the pool) */
-            HipResult *h = alloc_result_cols(out_types, n, device, stream);
-            if (!h) break;
-            HIP_OK(hipMemsetAsync(d_meta.p, 0, 8, stream));
-            ScanParams P;
-            std::memset(&P, 0, sizeof(P));
-            P.n = n;
-            P.n_preds = (int32_t)preds.size();
-            if (upload_patterns()) break;
-            for (size_t p = 0; p < preds.size(); p++) {
-                P.pred_col[p] = preds[p].col;
-                P.pred_cmp[p] = preds[p].cmp;
-                P.pred_i64[p] = preds[p].v_i64;
-                P.pred_f64[p] = preds[p].v_f64;
-                P.pred_pat[p] = (const uint8_t *)d_pats[p].p;
-                P.pred_plen[p] = preds[p].v_len;
-                P.pred_view[p] = st.views[preds[p].col];
+        if (d_meta.grow(8, stream)) return -1;
+        /* pass 1 would count; instead allocate full-capacity output and
+         * shrink by the counter (filters keep a bounded fraction and
+         * the buffers come from the pool) */
+        auto h = alloc_result_cols(out_types, n, device, stream);
+        if (!h) return -1;
+        HIP_OK(hipMemsetAsync(d_meta.p, 0, 8, stream));
+        ScanParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.n = n;
+        P.n_preds = (int32_t)preds.size();
+        if (upload_patterns()) return -1;
+        for (size_t p = 0; p < preds.size(); p++) {
+            P.pred_col[p] = preds[p].col;
+            P.pred_cmp[p] = preds[p].cmp;
+            P.pred_i64[p] = preds[p].v_i64;
+            P.pred_f64[p] = preds[p].v_f64;
+            P.pred_pat[p] = (const uint8_t *)d_pats[p].p;
+            P.pred_plen[p] = preds[p].v_len;
+            P.pred_view[p] = st.views[preds[p].col];
+        }
+        P.n_projs = (int32_t)projs.size();
+        for (size_t c = 0; c < projs.size(); c++) {
+            P.proj_op[c] = projs[c].op;
+            P.proj_a[c] = st.views[projs[c].a];
+            if (projs[c].op == GX_PROJ_DEC_TO_SCALED ||
+                projs[c].op == GX_PROJ_SCALED_TO_DEC)
+                P.proj_scale[c] = projs[c].c;   /* c = scale, not a col */
+            else if (projs[c].op != GX_PROJ_COPY)
+                P.proj_b[c] = st.views[projs[c].b];
+            if (projs[c].op == GX_PROJ_Q9_AMOUNT4) {
+                P.proj_c[c] = st.views[projs[c].c];
+                P.proj_d[c] = st.views[projs[c].d];
             }
-            P.n_projs = (int32_t)projs.size();
-            for (size_t c = 0; c < projs.size(); c++) {
-                P.proj_op[c] = projs[c].op;
-                P.proj_a[c] = st.views[projs[c].a];
-                if (projs[c].op == GX_PROJ_DEC_TO_SCALED ||
-                    projs[c].op == GX_PROJ_SCALED_TO_DEC)
-                    P.proj_scale[c] = projs[c].c;   /* c = scale, not a col */
-                else if (projs[c].op != GX_PROJ_COPY)
-                    P.proj_b[c] = st.views[projs[c].b];
-                if (projs[c].op == GX_PROJ_Q9_AMOUNT4) {
-                    P.proj_c[c] = st.views[projs[c].c];
-                    P.proj_d[c] = st.views[projs[c].d];
-                }
-                P.out_vals[c] = h->bufs[c * 2].p;
-                P.out_nulls[c] = (uint8_t *)h->bufs[c * 2 + 1].p;
-            }
-            P.cap = (uint32_t)n;
-            P.counter = (uint32_t *)d_meta.p;
-            P.err = (uint32_t *)d_meta.p + 1;
-            P.out_rowids = nullptr;
-            if (has_slice_out) {
-                if (d_rowids.grow((size_t)std::max<int64_t>(n, 1) * 4, stream))
-                    break;
-                P.out_rowids = (uint32_t *)d_rowids.p;
-            }
-            if (n > 0)
-                hipLaunchKernelGGL(k_scan, dim3(gx_grid(n)), dim3(256), 0,
-                                   stream, P);
-            uint32_t meta[2] = {0, 0};
-            if (n > 0) {
-                HIP_OK(hipMemcpyAsync(meta, d_meta.p, 8,
-                                      hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipStreamSynchronize(stream));
-            }
-            if (meta[1]) {
-                gx_set_err("wide DECIMAL: value exceeds 18 significant "
-                           "digits / the DecimalBox simple layout; the "
-                           "scaled-int64 fast path cannot represent it "
-                           "(reference falls back to full Decimal "
-                           "arithmetic, DecimalBox.java:43-71)");
-                free_result(h);
-                break;
-            }
-            uint32_t kept = meta[0];
-            h->res.chunk.n_rows = (int32_t)kept;
-            if (has_slice_out) {
-                bool fail = false;
-                for (size_t c = 0; c < projs.size(); c++) {
-                    if (out_types[c] != GX_SLICE) continue;
-                    if (gather_slice_col(st.views[projs[c].a],
-                                         (const uint32_t *)d_rowids.p, 0,
-                                         kept, h, c, d_scan_tmp, stream))
-                        fail = true;
-                }
-                if (fail) { free_result(h); break; }
-            }
-            *out = &h->res;
-            rc = 0;
-        } while (0);
-        st.release();
-        return rc;
+            P.out_vals[c] = h->bufs[c * 2].p;
+            P.out_nulls[c] = (uint8_t *)h->bufs[c * 2 + 1].p;
+        }
+        P.cap = (uint32_t)n;
+        P.counter = (uint32_t *)d_meta.p;
+        P.err = (uint32_t *)d_meta.p + 1;
+        P.out_rowids = nullptr;
+        if (has_slice_out) {
+            if (d_rowids.grow((size_t)std::max<int64_t>(n, 1) * 4, stream))
+                return -1;
+            P.out_rowids = (uint32_t *)d_rowids.p;
+        }
+        if (n > 0)
+            hipLaunchKernelGGL(k_scan, dim3(gx_grid(n)), dim3(256), 0,
+                               stream, P);
+        uint32_t meta[2] = {0, 0};
+        if (n > 0) {
+            HIP_OK(hipMemcpyAsync(meta, d_meta.p, 8,
+                                  hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+        }
+        if (meta[1]) {
+            gx_set_err("wide DECIMAL: value exceeds 18 significant "
+                       "digits / the DecimalBox simple layout; the "
+                       "scaled-int64 fast path cannot represent it "
+                       "(reference falls back to full Decimal "
+                       "arithmetic, DecimalBox.java:43-71)");
+            return -1;
+        }
+        uint32_t kept = meta[0];
+        h->res.chunk.n_rows = (int32_t)kept;
+        for (size_t c = 0; c < projs.size(); c++) {
+            if (out_types[c] != GX_SLICE) continue;
+            if (gather_slice_col(st.views[projs[c].a],
+                                 (const uint32_t *)d_rowids.p, 0, kept,
+                                 h.get(), c, d_scan_tmp, stream))
+                return -1;
+        }
+        give_result(std::move(h), out);
+        return 0;
     }
 };
 

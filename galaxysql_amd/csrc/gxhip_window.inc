@@ -19,15 +19,15 @@ namespace {
 
 #define GX_WIN_MAX_AGGS 16
 
-/* HIP_OK that breaks out of the surrounding do/while via `fail` */
-#define HIP_OK_BRK(call)                                                     \
-    do {                                                                     \
-        hipError_t _e = (call);                                              \
-        if (_e != hipSuccess) {                                              \
-            gx_set_err(std::string(#call) + ": " + hipGetErrorString(_e));   \
-            fail = true;                                                     \
-        }                                                                    \
-    } while (0)
+/* in-place inclusive scan of vals[0..n) that restarts at each change of seg */
+template <typename T, typename Op>
+int seg_scan(DevBuf &tmp, hipStream_t stream, const uint32_t *seg, T *vals,
+             int64_t n, Op op) {
+    return cub_run(tmp, stream, [&](void *t, size_t &b) {
+        return hipcub::DeviceScan::InclusiveScanByKey(
+            t, b, seg, vals, vals, op, n, hipcub::Equality(), stream);
+    });
+}
 
 struct WinPairI64 { long long v; long long seen; };
 struct WinPairF64 { double v; long long seen; };
@@ -323,11 +323,11 @@ struct WindowOp : gx_op {
     /* carry: device 1-row partition(+order) key + last scan value per agg
      * (+ one extra slot for the shared partition-head-position scan) */
     bool have_carry = false;
-    std::vector<DevBuf> carry_val, carry_data;   /* per carry col */
-    std::vector<DevBuf> carry_null;
     std::vector<int64_t> carry_slice_len;
+    /* last-allocated first (see DevBuf: destruction order and the pool) */
+    DevBuf d_scan_tmp2, d_segpos, d_vals, d_cont, d_seg, d_runheads, d_heads;
     std::vector<DevBuf> carry_state;
-    DevBuf d_heads, d_runheads, d_seg, d_cont, d_vals, d_segpos, d_scan_tmp2;
+    std::vector<DevBuf> carry_data, carry_null, carry_val; /* per carry col */
 
     WindowOp(const gx_window_cfg *c) : gx_op(OP_WINDOW, c->device, c->stream),
                                        cfg(*c) {
@@ -348,16 +348,6 @@ struct WindowOp : gx_op {
         carry_slice_len.assign(carry_cols_.size(), 0);
         carry_state.resize(aggs.size() + 1);  /* +1: shared seg-pos scan */
     }
-    ~WindowOp() override {
-        for (auto &b : carry_val) b.release();
-        for (auto &b : carry_null) b.release();
-        for (auto &b : carry_data) b.release();
-        for (auto &b : carry_state) b.release();
-        d_heads.release(); d_runheads.release(); d_seg.release();
-        d_cont.release(); d_vals.release(); d_segpos.release();
-        d_scan_tmp2.release();
-    }
-
     size_t scan_elem_size(int32_t func) const {
         switch (func) {
         case GX_AGG_COUNT_ROW: case GX_AGG_COUNT_COL: case GX_AGG_SUM_I64:
@@ -383,13 +373,7 @@ struct WindowOp : gx_op {
 
     template <typename T, typename Op>
     int scan_one(const uint32_t *seg, T *vals, int64_t n, Op op, size_t a) {
-        size_t tmp = 0;
-        HIP_OK(hipcub::DeviceScan::InclusiveScanByKey(
-            nullptr, tmp, seg, vals, vals, op, n, hipcub::Equality(), stream));
-        if (d_scan_tmp2.grow(tmp, stream)) return -1;
-        HIP_OK(hipcub::DeviceScan::InclusiveScanByKey(
-            d_scan_tmp2.p, tmp, seg, vals, vals, op, n, hipcub::Equality(),
-            stream));
+        if (seg_scan(d_scan_tmp2, stream, seg, vals, n, op)) return -1;
         if (have_carry)
             hipLaunchKernelGGL((k_win_carry_apply<T, Op>), dim3(gx_grid(n)),
                                dim3(256), 0, stream, seg,
@@ -419,268 +403,233 @@ struct WindowOp : gx_op {
             }
         }
         if (n == 0) {
-            HipResult *h = alloc_result_cols(otypes, 0, device, stream);
+            auto h = alloc_result_cols(otypes, 0, device, stream);
             if (!h) return -1;
-            *out = &h->res;
+            give_result(std::move(h), out);
             return 0;
         }
         StagedChunk st;
         if (st.stage(ch, stream)) return -1;
-        int rc = -1;
-        do {
-            /* 1. heads + segment ids */
-            if (d_heads.grow((size_t)n * 4, stream) ||
-                d_seg.grow((size_t)n * 4, stream) ||
-                d_cont.grow(4, stream)) break;
-            WinHeadParams H;
-            std::memset(&H, 0, sizeof(H));
-            H.n = n;
-            H.n_part = (int32_t)part_cols_.size();
-            for (size_t k = 0; k < part_cols_.size(); k++) {
-                H.cols[k] = st.views[part_cols_[k]];
-                if (have_carry) H.carry[k] = carry_view(k, H.cols[k]);
+        /* 1. heads + segment ids */
+        if (d_heads.grow((size_t)n * 4, stream) ||
+            d_seg.grow((size_t)n * 4, stream) ||
+            d_cont.grow(4, stream)) return -1;
+        WinHeadParams H;
+        std::memset(&H, 0, sizeof(H));
+        H.n = n;
+        H.n_part = (int32_t)part_cols_.size();
+        for (size_t k = 0; k < part_cols_.size(); k++) {
+            H.cols[k] = st.views[part_cols_[k]];
+            if (have_carry) H.carry[k] = carry_view(k, H.cols[k]);
+        }
+        H.have_carry = have_carry;
+        H.heads = (uint32_t *)d_heads.p;
+        H.continues = (uint32_t *)d_cont.p;
+        if (has_rank) {
+            if (d_runheads.grow((size_t)n * 4, stream)) return -1;
+            H.n_order = (int32_t)order_cols_.size();
+            for (size_t k = 0; k < order_cols_.size(); k++) {
+                H.ocols[k] = st.views[order_cols_[k]];
+                if (have_carry)
+                    H.ocarry[k] = carry_view(part_cols_.size() + k,
+                                             H.ocols[k]);
             }
-            H.have_carry = have_carry;
-            H.heads = (uint32_t *)d_heads.p;
-            H.continues = (uint32_t *)d_cont.p;
-            if (has_rank) {
-                if (d_runheads.grow((size_t)n * 4, stream)) break;
-                H.n_order = (int32_t)order_cols_.size();
-                for (size_t k = 0; k < order_cols_.size(); k++) {
-                    H.ocols[k] = st.views[order_cols_[k]];
-                    if (have_carry)
-                        H.ocarry[k] = carry_view(part_cols_.size() + k,
-                                                 H.ocols[k]);
-                }
-                H.run_heads = (uint32_t *)d_runheads.p;
-            }
-            hipLaunchKernelGGL(k_win_heads, dim3(gx_grid(n)), dim3(256), 0,
-                               stream, H);
-            size_t tmp = 0;
-            HIP_OK(hipcub::DeviceScan::InclusiveSum(
-                nullptr, tmp, (uint32_t *)d_heads.p, (uint32_t *)d_seg.p, n,
-                stream));
-            if (d_scan_tmp2.grow(tmp, stream)) break;
-            HIP_OK(hipcub::DeviceScan::InclusiveSum(
-                d_scan_tmp2.p, tmp, (uint32_t *)d_heads.p,
-                (uint32_t *)d_seg.p, n, stream));
+            H.run_heads = (uint32_t *)d_runheads.p;
+        }
+        hipLaunchKernelGGL(k_win_heads, dim3(gx_grid(n)), dim3(256), 0,
+                           stream, H);
+        if (cub_run(d_scan_tmp2, stream, [&](void *t, size_t &b) {
+                return hipcub::DeviceScan::InclusiveSum(
+                    t, b, (uint32_t *)d_heads.p, (uint32_t *)d_seg.p, n,
+                    stream);
+            }))
+            return -1;
 
-            /* 1b. rank family: the shared partition-head-position scan
-             * S[i] = GLOBAL index+1 of the current partition's first row
-             * (max-scan over seg; carry slot aggs.size()) */
-            if (has_rank) {
-                if (d_segpos.grow((size_t)n * 8, stream)) break;
-                auto *sp = (unsigned long long *)d_segpos.p;
-                hipLaunchKernelGGL(k_win_map_headpos, dim3(gx_grid(n)),
-                                   dim3(256), 0, stream,
-                                   (const uint32_t *)d_heads.p, g_base, n,
-                                   sp);
-                if (scan_one((const uint32_t *)d_seg.p, sp, n, WinMaxU64(),
-                             aggs.size()))
-                    break;
-            }
+        /* 1b. rank family: the shared partition-head-position scan
+         * S[i] = GLOBAL index+1 of the current partition's first row
+         * (max-scan over seg; carry slot aggs.size()) */
+        if (has_rank) {
+            if (d_segpos.grow((size_t)n * 8, stream)) return -1;
+            auto *sp = (unsigned long long *)d_segpos.p;
+            hipLaunchKernelGGL(k_win_map_headpos, dim3(gx_grid(n)),
+                               dim3(256), 0, stream,
+                               (const uint32_t *)d_heads.p, g_base, n,
+                               sp);
+            if (scan_one((const uint32_t *)d_seg.p, sp, n, WinMaxU64(),
+                         aggs.size()))
+                return -1;
+        }
 
-            /* 2. result shell + pass-through input columns */
-            HipResult *h = alloc_result_cols(otypes, n, device, stream);
-            if (!h) break;
-            bool fail = false;
-            for (size_t c = 0; c < input_types.size() && !fail; c++) {
-                const DevColView &v = st.views[c];
-                if (input_types[c] == GX_SLICE) {
-                    /* identity gather (copies offsets + bytes) */
-                    DevBuf iota;
-                    if (iota.grow((size_t)n * 4, stream)) { fail = true; break; }
-                    hipLaunchKernelGGL(k_iota, dim3(gx_grid(n)), dim3(256), 0,
-                                       stream, (uint32_t *)iota.p, n);
-                    if (gather_slice_col(v, (const uint32_t *)iota.p, 0, n, h,
-                                         c, d_scan_tmp2, stream))
-                        fail = true;
-                    iota.release();
+        /* 2. result shell + pass-through input columns */
+        auto h = alloc_result_cols(otypes, n, device, stream);
+        if (!h) return -1;
+        if (copy_input_cols(input_types, st.views.data(), n, h.get(),
+                            d_scan_tmp2, stream))
+            return -1;
+
+        /* 3. per window function: map -> scan-by-segment -> emit */
+        const uint32_t *seg = (const uint32_t *)d_seg.p;
+        for (size_t a = 0; a < aggs.size(); a++) {
+            size_t col = input_types.size() + a;
+            int32_t f0 = aggs[a].func;
+            if (f0 == GX_AGG_RANK || f0 == GX_AGG_DENSE_RANK) {
+                if (reset_[a]) {
+                    /* resetAccumulators: every row is rank 1 */
+                    hipLaunchKernelGGL(k_win_fill_i64, dim3(gx_grid(n)),
+                                       dim3(256), 0, stream, (int64_t)1,
+                                       n, (int64_t *)h->bufs[col * 2].p,
+                                       (uint8_t *)h->bufs[col * 2 + 1].p);
                     continue;
                 }
-                size_t es = gx_fixed_size(input_types[c]);
-                HIP_OK_BRK(hipMemcpyAsync(h->bufs[c * 2].p, v.values,
-                                          (size_t)n * es,
-                                          hipMemcpyDeviceToDevice, stream));
-                if (v.nulls) {
-                    HIP_OK_BRK(hipMemcpyAsync(h->bufs[c * 2 + 1].p, v.nulls,
-                                              (size_t)n,
-                                              hipMemcpyDeviceToDevice, stream));
+                if (d_vals.grow((size_t)n * 8, stream)) return -1;
+                auto *vals = (unsigned long long *)d_vals.p;
+                if (f0 == GX_AGG_RANK) {
+                    hipLaunchKernelGGL(k_win_map_headpos,
+                                       dim3(gx_grid(n)), dim3(256), 0,
+                                       stream,
+                                       (const uint32_t *)d_runheads.p,
+                                       g_base, n, vals);
+                    if (scan_one((const uint32_t *)d_seg.p, vals, n,
+                                 WinMaxU64(), a)) return -1;
+                    hipLaunchKernelGGL(k_win_emit_rank, dim3(gx_grid(n)),
+                                       dim3(256), 0, stream, vals,
+                                       (const unsigned long long *)d_segpos.p,
+                                       n, (int64_t *)h->bufs[col * 2].p,
+                                       (uint8_t *)h->bufs[col * 2 + 1].p);
                 } else {
-                    HIP_OK_BRK(hipMemsetAsync(h->bufs[c * 2 + 1].p, 0,
-                                              (size_t)n, stream));
-                }
-            }
-            if (fail) { free_result(h); break; }
-
-            /* 3. per window function: map -> scan-by-segment -> emit */
-            const uint32_t *seg = (const uint32_t *)d_seg.p;
-            for (size_t a = 0; a < aggs.size() && !fail; a++) {
-                size_t col = input_types.size() + a;
-                int32_t f0 = aggs[a].func;
-                if (f0 == GX_AGG_RANK || f0 == GX_AGG_DENSE_RANK) {
-                    if (reset_[a]) {
-                        /* resetAccumulators: every row is rank 1 */
-                        hipLaunchKernelGGL(k_win_fill_i64, dim3(gx_grid(n)),
-                                           dim3(256), 0, stream, (int64_t)1,
-                                           n, (int64_t *)h->bufs[col * 2].p,
-                                           (uint8_t *)h->bufs[col * 2 + 1].p);
-                        continue;
-                    }
-                    if (d_vals.grow((size_t)n * 8, stream)) { fail = true; break; }
-                    auto *vals = (unsigned long long *)d_vals.p;
-                    if (f0 == GX_AGG_RANK) {
-                        hipLaunchKernelGGL(k_win_map_headpos,
-                                           dim3(gx_grid(n)), dim3(256), 0,
-                                           stream,
-                                           (const uint32_t *)d_runheads.p,
-                                           g_base, n, vals);
-                        if (scan_one((const uint32_t *)d_seg.p, vals, n,
-                                     WinMaxU64(), a)) { fail = true; break; }
-                        hipLaunchKernelGGL(k_win_emit_rank, dim3(gx_grid(n)),
-                                           dim3(256), 0, stream, vals,
-                                           (const unsigned long long *)d_segpos.p,
-                                           n, (int64_t *)h->bufs[col * 2].p,
-                                           (uint8_t *)h->bufs[col * 2 + 1].p);
-                    } else {
-                        hipLaunchKernelGGL(k_win_map_flags, dim3(gx_grid(n)),
-                                           dim3(256), 0, stream,
-                                           (const uint32_t *)d_runheads.p, n,
-                                           vals);
-                        if (scan_one((const uint32_t *)d_seg.p, vals, n,
-                                     WinSumU64(), a)) { fail = true; break; }
-                        hipLaunchKernelGGL(k_win_emit_u64, dim3(gx_grid(n)),
-                                           dim3(256), 0, stream, vals, n,
-                                           (int64_t *)h->bufs[col * 2].p,
-                                           (uint8_t *)h->bufs[col * 2 + 1].p);
-                    }
-                    continue;
-                }
-                DevColView in{};
-                if (aggs[a].input_col >= 0) in = st.views[aggs[a].input_col];
-                size_t es = scan_elem_size(aggs[a].func);
-                if (d_vals.grow((size_t)n * es, stream)) { fail = true; break; }
-                int32_t f = aggs[a].func;
-                if (es == 8) {
-                    auto *vals = (unsigned long long *)d_vals.p;
-                    hipLaunchKernelGGL(k_win_map_u64, dim3(gx_grid(n)),
-                                       dim3(256), 0, stream, in, f, n, vals);
-                    if (!reset_[a]) {
-                        int r = f == GX_AGG_BIT_AND
-                            ? scan_one(seg, vals, n, WinAndU64(), a)
-                            : f == GX_AGG_BIT_OR
-                            ? scan_one(seg, vals, n, WinOrU64(), a)
-                            : f == GX_AGG_BIT_XOR
-                            ? scan_one(seg, vals, n, WinXorU64(), a)
-                            : scan_one(seg, vals, n, WinSumU64(), a);
-                        if (r) { fail = true; break; }
-                    }
+                    hipLaunchKernelGGL(k_win_map_flags, dim3(gx_grid(n)),
+                                       dim3(256), 0, stream,
+                                       (const uint32_t *)d_runheads.p, n,
+                                       vals);
+                    if (scan_one((const uint32_t *)d_seg.p, vals, n,
+                                 WinSumU64(), a)) return -1;
                     hipLaunchKernelGGL(k_win_emit_u64, dim3(gx_grid(n)),
                                        dim3(256), 0, stream, vals, n,
                                        (int64_t *)h->bufs[col * 2].p,
                                        (uint8_t *)h->bufs[col * 2 + 1].p);
-                } else if (f == GX_AGG_MIN_I64 || f == GX_AGG_MAX_I64 ||
-                           f == GX_AGG_SUM_I64N) {
-                    auto *vals = (WinPairI64 *)d_vals.p;
-                    hipLaunchKernelGGL(k_win_map_pair_i64, dim3(gx_grid(n)),
-                                       dim3(256), 0, stream, in, n, vals);
-                    if (!reset_[a]) {
-                        int r = f == GX_AGG_MIN_I64
-                            ? scan_one(seg, vals, n, WinMinI64Op(), a)
-                            : f == GX_AGG_MAX_I64
-                            ? scan_one(seg, vals, n, WinMaxI64Op(), a)
-                            : scan_one(seg, vals, n, WinSumI64Op(), a);
-                        if (r) { fail = true; break; }
-                    }
-                    hipLaunchKernelGGL(k_win_emit_pair_i64, dim3(gx_grid(n)),
-                                       dim3(256), 0, stream, vals, n,
-                                       (int64_t *)h->bufs[col * 2].p,
+                }
+                continue;
+            }
+            DevColView in{};
+            if (aggs[a].input_col >= 0) in = st.views[aggs[a].input_col];
+            size_t es = scan_elem_size(aggs[a].func);
+            if (d_vals.grow((size_t)n * es, stream)) return -1;
+            int32_t f = aggs[a].func;
+            if (es == 8) {
+                auto *vals = (unsigned long long *)d_vals.p;
+                hipLaunchKernelGGL(k_win_map_u64, dim3(gx_grid(n)),
+                                   dim3(256), 0, stream, in, f, n, vals);
+                if (!reset_[a]) {
+                    int r = f == GX_AGG_BIT_AND
+                        ? scan_one(seg, vals, n, WinAndU64(), a)
+                        : f == GX_AGG_BIT_OR
+                        ? scan_one(seg, vals, n, WinOrU64(), a)
+                        : f == GX_AGG_BIT_XOR
+                        ? scan_one(seg, vals, n, WinXorU64(), a)
+                        : scan_one(seg, vals, n, WinSumU64(), a);
+                    if (r) return -1;
+                }
+                hipLaunchKernelGGL(k_win_emit_u64, dim3(gx_grid(n)),
+                                   dim3(256), 0, stream, vals, n,
+                                   (int64_t *)h->bufs[col * 2].p,
+                                   (uint8_t *)h->bufs[col * 2 + 1].p);
+            } else if (f == GX_AGG_MIN_I64 || f == GX_AGG_MAX_I64 ||
+                       f == GX_AGG_SUM_I64N) {
+                auto *vals = (WinPairI64 *)d_vals.p;
+                hipLaunchKernelGGL(k_win_map_pair_i64, dim3(gx_grid(n)),
+                                   dim3(256), 0, stream, in, n, vals);
+                if (!reset_[a]) {
+                    int r = f == GX_AGG_MIN_I64
+                        ? scan_one(seg, vals, n, WinMinI64Op(), a)
+                        : f == GX_AGG_MAX_I64
+                        ? scan_one(seg, vals, n, WinMaxI64Op(), a)
+                        : scan_one(seg, vals, n, WinSumI64Op(), a);
+                    if (r) return -1;
+                }
+                hipLaunchKernelGGL(k_win_emit_pair_i64, dim3(gx_grid(n)),
+                                   dim3(256), 0, stream, vals, n,
+                                   (int64_t *)h->bufs[col * 2].p,
+                                   (uint8_t *)h->bufs[col * 2 + 1].p);
+            } else {
+                auto *vals = (WinPairF64 *)d_vals.p;
+                hipLaunchKernelGGL(k_win_map_pair_f64, dim3(gx_grid(n)),
+                                   dim3(256), 0, stream, in, n, vals);
+                if (!reset_[a]) {
+                    int r = f == GX_AGG_MIN_F64
+                        ? scan_one(seg, vals, n, WinMinF64Op(), a)
+                        : f == GX_AGG_MAX_F64
+                        ? scan_one(seg, vals, n, WinMaxF64Op(), a)
+                        : f == GX_AGG_AVG_F64
+                        ? scan_one(seg, vals, n, WinAvgF64Op(), a)
+                        : scan_one(seg, vals, n, WinSumF64Op(), a);
+                    if (r) return -1;
+                }
+                if (f == GX_AGG_AVG_F64)
+                    hipLaunchKernelGGL(k_win_emit_avg_f64,
+                                       dim3(gx_grid(n)), dim3(256), 0,
+                                       stream, vals, n,
+                                       (double *)h->bufs[col * 2].p,
                                        (uint8_t *)h->bufs[col * 2 + 1].p);
-                } else {
-                    auto *vals = (WinPairF64 *)d_vals.p;
-                    hipLaunchKernelGGL(k_win_map_pair_f64, dim3(gx_grid(n)),
-                                       dim3(256), 0, stream, in, n, vals);
-                    if (!reset_[a]) {
-                        int r = f == GX_AGG_MIN_F64
-                            ? scan_one(seg, vals, n, WinMinF64Op(), a)
-                            : f == GX_AGG_MAX_F64
-                            ? scan_one(seg, vals, n, WinMaxF64Op(), a)
-                            : f == GX_AGG_AVG_F64
-                            ? scan_one(seg, vals, n, WinAvgF64Op(), a)
-                            : scan_one(seg, vals, n, WinSumF64Op(), a);
-                        if (r) { fail = true; break; }
-                    }
-                    if (f == GX_AGG_AVG_F64)
-                        hipLaunchKernelGGL(k_win_emit_avg_f64,
-                                           dim3(gx_grid(n)), dim3(256), 0,
-                                           stream, vals, n,
-                                           (double *)h->bufs[col * 2].p,
-                                           (uint8_t *)h->bufs[col * 2 + 1].p);
-                    else
-                        hipLaunchKernelGGL(k_win_emit_pair_f64,
-                                           dim3(gx_grid(n)), dim3(256), 0,
-                                           stream, vals, n,
-                                           (double *)h->bufs[col * 2].p,
-                                           (uint8_t *)h->bufs[col * 2 + 1].p);
-                }
+                else
+                    hipLaunchKernelGGL(k_win_emit_pair_f64,
+                                       dim3(gx_grid(n)), dim3(256), 0,
+                                       stream, vals, n,
+                                       (double *)h->bufs[col * 2].p,
+                                       (uint8_t *)h->bufs[col * 2 + 1].p);
             }
-            if (fail) { free_result(h); break; }
+        }
 
-            /* 4. save the last row's partition(+order) key as carry */
-            for (size_t k = 0; k < carry_cols_.size() && !fail; k++) {
-                const DevColView &v = st.views[carry_cols_[k]];
-                if (carry_null[k].grow(1, stream)) { fail = true; break; }
-                if (v.type == GX_SLICE) {
-                    /* need host lengths for the byte copy */
-                    int32_t offs[2] = {0, 0};
-                    HIP_OK_BRK(hipMemcpyAsync(&offs[1], v.offsets + (n - 1), 4,
-                                              hipMemcpyDeviceToHost, stream));
-                    if (n > 1)
-                        HIP_OK_BRK(hipMemcpyAsync(&offs[0], v.offsets + (n - 2),
-                                                  4, hipMemcpyDeviceToHost,
-                                                  stream));
-                    HIP_OK_BRK(hipStreamSynchronize(stream));
-                    int32_t len = offs[1] - offs[0];
-                    carry_slice_len[k] = len;
-                    if (carry_val[k].grow(4, stream) ||
-                        carry_data[k].grow((size_t)std::max(len, 1), stream)) {
-                        fail = true; break;
-                    }
-                    HIP_OK_BRK(hipMemcpyAsync(carry_val[k].p, &len, 4,
-                                              hipMemcpyHostToDevice, stream));
-                    if (len > 0)
-                        HIP_OK_BRK(hipMemcpyAsync(carry_data[k].p,
-                                                  v.bytes + offs[0],
-                                                  (size_t)len,
-                                                  hipMemcpyDeviceToDevice,
-                                                  stream));
-                    uint8_t nn = 0;
-                    if (v.nulls)
-                        HIP_OK_BRK(hipMemcpyAsync(carry_null[k].p,
-                                                  v.nulls + (n - 1), 1,
-                                                  hipMemcpyDeviceToDevice,
-                                                  stream));
-                    else
-                        HIP_OK_BRK(hipMemcpyAsync(carry_null[k].p, &nn, 1,
-                                                  hipMemcpyHostToDevice,
-                                                  stream));
-                } else {
-                    if (carry_val[k].grow(8, stream)) { fail = true; break; }
-                    hipLaunchKernelGGL(k_win_save_carry_fixed, dim3(1),
-                                       dim3(64), 0, stream, v, n - 1,
-                                       carry_val[k].p,
-                                       (uint8_t *)carry_null[k].p);
-                }
+        /* 4. save the last row's partition(+order) key as carry */
+        for (size_t k = 0; k < carry_cols_.size(); k++) {
+            const DevColView &v = st.views[carry_cols_[k]];
+            if (carry_null[k].grow(1, stream)) return -1;
+            if (v.type == GX_SLICE) {
+                /* need host lengths for the byte copy */
+                int32_t offs[2] = {0, 0};
+                HIP_OK(hipMemcpyAsync(&offs[1], v.offsets + (n - 1), 4,
+                                      hipMemcpyDeviceToHost, stream));
+                if (n > 1)
+                    HIP_OK(hipMemcpyAsync(&offs[0], v.offsets + (n - 2),
+                                          4, hipMemcpyDeviceToHost,
+                                          stream));
+                HIP_OK(hipStreamSynchronize(stream));
+                int32_t len = offs[1] - offs[0];
+                carry_slice_len[k] = len;
+                if (carry_val[k].grow(4, stream) ||
+                    carry_data[k].grow((size_t)std::max(len, 1), stream))
+                    return -1;
+                HIP_OK(hipMemcpyAsync(carry_val[k].p, &len, 4,
+                                      hipMemcpyHostToDevice, stream));
+                if (len > 0)
+                    HIP_OK(hipMemcpyAsync(carry_data[k].p,
+                                          v.bytes + offs[0],
+                                          (size_t)len,
+                                          hipMemcpyDeviceToDevice,
+                                          stream));
+                uint8_t nn = 0;
+                if (v.nulls)
+                    HIP_OK(hipMemcpyAsync(carry_null[k].p,
+                                          v.nulls + (n - 1), 1,
+                                          hipMemcpyDeviceToDevice,
+                                          stream));
+                else
+                    HIP_OK(hipMemcpyAsync(carry_null[k].p, &nn, 1,
+                                          hipMemcpyHostToDevice,
+                                          stream));
+            } else {
+                if (carry_val[k].grow(8, stream)) return -1;
+                hipLaunchKernelGGL(k_win_save_carry_fixed, dim3(1),
+                                   dim3(64), 0, stream, v, n - 1,
+                                   carry_val[k].p,
+                                   (uint8_t *)carry_null[k].p);
             }
-            if (fail) { free_result(h); break; }
-            HIP_OK(hipStreamSynchronize(stream));
-            have_carry = true;
-            g_base += n;
-            *out = &h->res;
-            rc = 0;
-        } while (0);
-        st.release();
-        return rc;
+        }
+        /* the staged chunk is freed on return: drain first */
+        HIP_OK(hipStreamSynchronize(stream));
+        have_carry = true;
+        g_base += n;
+        give_result(std::move(h), out);
+        return 0;
     }
 };
 
