@@ -245,6 +245,34 @@ FRAME_WHOLE_PARTITION, FRAME_ROWS_SLIDING, FRAME_ROWS_UNBOUNDED_FOLLOWING = \
 # SQL SUM over integers, NULL-init (the Sum family AggregateUtils maps
 # SqlKind.SUM to); SUM_I64 is SqlKind.SUM0 (Long2LongSum0, init 0)
 SUM_I64N = 22
+# DISTINCT aggregates (the named reference class with isDistinct=true; see
+# gx_agg_func in include/gxop.h). gxop_agg only; a distinct aggregate cannot
+# be split partial->final (exchange.final_agg_specs).
+(COUNT_DISTINCT, SUM_I64_DISTINCT, SUM_I64N_DISTINCT, SUM_F64_DISTINCT,
+ AVG_F64_DISTINCT) = range(23, 28)
+DISTINCT_FUNCS = frozenset((COUNT_DISTINCT, SUM_I64_DISTINCT,
+                            SUM_I64N_DISTINCT, SUM_F64_DISTINCT,
+                            AVG_F64_DISTINCT))
+_DISTINCT_OF = {COUNT_COL: COUNT_DISTINCT, SUM_I64: SUM_I64_DISTINCT,
+                SUM_I64N: SUM_I64N_DISTINCT, SUM_F64: SUM_F64_DISTINCT,
+                AVG_F64: AVG_F64_DISTINCT}
+# idempotent under duplicates, so DISTINCT is the plain func; BIT_XOR is not
+# idempotent, but the reference's BitXor constructors take no distinct flag
+# (AggregateUtils.java:290-303), so its DISTINCT is plain BIT_XOR too
+_DISTINCT_IS_PLAIN = frozenset((MIN_I64, MAX_I64, MIN_F64, MAX_F64, BIT_AND,
+                                BIT_OR, BIT_XOR))
+
+
+def distinct_of(func):
+    """The func a shim passes for `func` constructed with isDistinct=true.
+    Raises ValueError where no GPU form exists (COUNT_ROW, i.e. CountRow and
+    multi-column COUNT(DISTINCT a, b); window-only funcs): those plans stay
+    on the CPU."""
+    if func in _DISTINCT_OF:
+        return _DISTINCT_OF[func]
+    if func in _DISTINCT_IS_PLAIN:
+        return func
+    raise ValueError(f"agg func {func} has no DISTINCT form")
 
 ORACLE_PATH = os.path.join(_REPO, "oracle", "libgxoracle.so")
 HIP_PATH = os.path.join(_REPO, "galaxysql_amd", "csrc", "libgxhip.so")

@@ -533,14 +533,210 @@ __global__ void k_agg_emit(const unsigned long long *records, int32_t stride,
     }
 }
 
+/* ---- DISTINCT aggregates ------------------------------------------------
+ * AggOpenHashMap.putChunk asks a per-aggregator DistinctSet — itself a
+ * GroupOpenHashMap over (groupId, value) — whether the pair was seen, and
+ * accumulates only when it was not (AggOpenHashMap.java:100-139,
+ * operator/util/DistinctSet.java). Here: one device set per distinct INPUT
+ * COLUMN (COUNT(DISTINCT x), SUM(DISTINCT x) share it), built like the group
+ * table above and for the same reasons. Per consumed chunk, once the chunk's
+ * gids are final:
+ *   k_dist_pack:   one persistent 16-B record {gid, hash, value} per row,
+ *                  resident BEFORE the insert launches (a losing lane always
+ *                  compares against data already there, never waits).
+ *   k_dist_insert: claim an 8-B slot {tag:32, drow+1:32} with one 64-bit
+ *                  CAS; the winner applies that column's distinct aggs to
+ *                  records[gid] through agg_apply (base funcs); a lane that
+ *                  finds an equal owner drops its row. NULL values never
+ *                  enter the set.
+ * A bounded probe sets the overflow flag and leaves the row PENDING; the
+ * host grows the slot array x4 (owners re-inserted by drow — distinct by
+ * construction, no compare) and reruns only the pending rows, so every row
+ * resolves exactly once and a win accumulates exactly once.
+ * Value hash/equality are col_hash / col_eq of the value's type, i.e. what
+ * a group-key column of that type gets. */
+
+struct __align__(16) DistRec {
+    uint32_t gid;
+    int32_t hash;             /* pair hash; kept so growth never recomputes */
+    unsigned long long value; /* fixed-width value bits (I32 zero-extended);
+                                 unused for SLICE (compared via the store) */
+};
+
+#define GX_DIST_PENDING 0
+#define GX_DIST_DONE 1
+
+__device__ static inline int32_t dist_pair_hash(uint32_t gid, int32_t vh) {
+    /* gids are dense small integers: scramble before combining, or
+     * (gid, v) and (gid+1, v-31) would share a probe chain */
+    return (int32_t)((uint32_t)gx_murmur3((int32_t)gid) * 31u + (uint32_t)vh);
+}
+
+__global__ void k_dist_pack(DevColView in, int64_t n, int64_t base,
+                            const uint32_t *slot_of_row, const AggSlot *slots,
+                            DistRec *recs, uint8_t *status) {
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        DistRec rec;
+        rec.gid = slot_of_row ? slots[slot_of_row[r]].gid : 0u;
+        rec.hash = 0;
+        rec.value = 0ull;
+        const bool isnull = col_is_null(in, r);
+        if (!isnull) {
+            rec.hash = dist_pair_hash(rec.gid, col_hash(in, r));
+            switch (in.type) {
+            case GX_I64: case GX_F64:
+                rec.value = ((const unsigned long long *)in.values)[r];
+                break;
+            case GX_I32:
+                rec.value = ((const uint32_t *)in.values)[r];
+                break;
+            }
+        }
+        recs[base + r] = rec;
+        status[r] = isnull ? GX_DIST_DONE : GX_DIST_PENDING;
+    }
+}
+
+struct DistInsertParams {
+    unsigned long long *slots;  /* {tag:32, drow+1:32}; 0 = empty */
+    uint32_t mask;
+    int32_t vtype;
+    const DistRec *recs;        /* persistent, indexed by drow */
+    DevColView store;           /* SLICE: persistent value column (by drow) */
+    int64_t base_drow;
+    int64_t n;
+    uint8_t *status;            /* per chunk row: PENDING / DONE */
+    uint32_t *ctl;              /* [0] overflow flag, [1] owners (occupancy) */
+    AggAccumParams A;           /* this set's aggs, base funcs */
+};
+
+__device__ static inline bool dist_equal(const DistInsertParams &P,
+                                         const DistRec &mine, int64_t drow,
+                                         int64_t owner) {
+    const DistRec o = P.recs[owner];
+    if (o.gid != mine.gid) return false;
+    switch (P.vtype) {
+    case GX_F64: /* col_eq: IEEE ==, as for an F64 group key */
+        return __builtin_bit_cast(double, o.value) ==
+               __builtin_bit_cast(double, mine.value);
+    case GX_SLICE:
+        return col_eq(P.store, owner, P.store, drow);
+    default:
+        return o.value == mine.value;
+    }
+}
+
+__global__ void k_dist_insert(DistInsertParams P) {
+    __shared__ uint32_t block_wins;
+    if (threadIdx.x == 0) block_wins = 0;
+    __syncthreads();
+    uint32_t wins = 0;
+    const uint32_t max_probes = P.mask < 1023u ? P.mask : 1023u;
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < P.n;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        if (P.status[r] != GX_DIST_PENDING) continue;
+        /* the table is already known to be too small: leave the rest
+         * PENDING instead of walking a full table 1K slots per row (a stale
+         * read only costs this row its probes) */
+        if (__hip_atomic_load(P.ctl, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT))
+            continue;
+        const int64_t drow = P.base_drow + r;
+        const DistRec mine = P.recs[drow];
+        const uint32_t tag = agg_tag(mine.hash);
+        const unsigned long long claim =
+            ((unsigned long long)tag << 32) | (uint32_t)(drow + 1);
+        uint32_t slot = (uint32_t)gx_mix(mine.hash) & P.mask;
+        uint32_t probes = 0;
+        while (true) {
+            /* plain load first: claims are monotonic (see k_agg_insert) */
+            unsigned long long old = P.slots[slot];
+            if (old == 0ull) old = atomicCAS(&P.slots[slot], 0ull, claim);
+            if (old == 0ull) {
+                /* first of its (group, value): the only lane that counts */
+                agg_apply(P.A, mine.gid, r);
+                wins++;
+                P.status[r] = GX_DIST_DONE;
+                break;
+            }
+            if ((uint32_t)(old >> 32) == tag &&
+                dist_equal(P, mine, drow, (int64_t)(uint32_t)old - 1)) {
+                P.status[r] = GX_DIST_DONE; /* seen before: drop */
+                break;
+            }
+            if (++probes > max_probes) {
+                P.ctl[0] = 1u; /* stays PENDING for the rerun after growth */
+                break;
+            }
+            slot = (slot + 1) & P.mask;
+        }
+    }
+    /* occupancy: one global add per block, not a hot word per claim */
+    if (wins) atomicAdd(&block_wins, wins);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_wins) atomicAdd(P.ctl + 1, block_wins);
+}
+
+/* growth: re-insert every owner by drow into the larger slot array */
+__global__ void k_dist_rehash(const unsigned long long *old_slots,
+                              int64_t n_old, unsigned long long *slots,
+                              uint32_t mask, const DistRec *recs) {
+    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n_old;
+         s += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long c = old_slots[s];
+        if (c == 0ull) continue;
+        const int32_t h = recs[(int64_t)(uint32_t)c - 1].hash;
+        uint32_t slot = (uint32_t)gx_mix(h) & mask;
+        while (atomicCAS(&slots[slot], 0ull, c) != 0ull)
+            slot = (slot + 1) & mask;
+    }
+}
+
+/* DISTINCT func -> the base func whose state/accumulate/emit it shares;
+ * -1 for a plain func */
+static inline int32_t agg_distinct_base(int32_t f) {
+    switch (f) {
+    case GX_AGG_COUNT_DISTINCT: return GX_AGG_COUNT_COL;
+    case GX_AGG_SUM_I64_DISTINCT: return GX_AGG_SUM_I64;
+    case GX_AGG_SUM_I64N_DISTINCT: return GX_AGG_SUM_I64N;
+    case GX_AGG_SUM_F64_DISTINCT: return GX_AGG_SUM_F64;
+    case GX_AGG_AVG_F64_DISTINCT: return GX_AGG_AVG_F64;
+    default: return -1;
+    }
+}
+/* the other ops' creates reject these (gxop_agg only) */
+static inline bool gx_agg_is_distinct(int32_t f) {
+    return agg_distinct_base(f) >= 0;
+}
+
+/* host side of one distinct set (one per distinct input column) */
+struct DistSet {
+    int32_t input_col = -1;
+    int32_t vtype = GX_I64;
+    std::vector<int32_t> agg_idx;  /* the op's aggs fed by this set */
+    DevBuf d_ctl, d_slots, d_recs;
+    DevStore store;                /* SLICE values, appended per chunk */
+    int64_t n_slots = 0;
+    int64_t n_drows = 0;           /* records written so far */
+    uint32_t owners = 0;           /* occupancy, read back per attempt */
+};
+
 struct AggOp : gx_op {
     gx_agg_cfg cfg;
     std::vector<int32_t> group_cols_, input_types;
     std::vector<gx_agg_spec> aggs;
 
+    /* DISTINCT: aggs[] holds BASE funcs (layout, accumulate and emission
+     * work by base func); is_distinct[a] marks the ones fed by a DistSet */
+    std::vector<uint8_t> is_distinct;
+    bool has_distinct = false;
+
     /* device buffers, last-allocated first (see DevBuf: destruction order
      * and the pool); d_slots / d_records, d_hashes / d_slotidx and
      * d_krow_of_gid / d_slot_of_gid share a size class */
+    std::vector<DistSet> dsets; /* one per distinct input column */
+    DevBuf d_dstatus;           /* per chunk row: distinct pass status */
     DevBuf d_slot_of_gid;      /* slot mode: record index per gid */
     DevBuf d_records;          /* AoS per-group state records */
     DevBuf d_slotidx, d_total, d_tiles, d_hashes, d_krow_of_gid, d_slots;
@@ -566,6 +762,26 @@ struct AggOp : gx_op {
         group_cols_.assign(c->group_cols, c->group_cols + c->n_group_cols);
         input_types.assign(c->input_types, c->input_types + c->n_input_cols);
         aggs.assign(c->aggs, c->aggs + c->n_aggs);
+        is_distinct.assign(aggs.size(), 0);
+        for (size_t a = 0; a < aggs.size(); a++) {
+            int32_t base = agg_distinct_base(aggs[a].func);
+            if (base < 0) continue;
+            aggs[a].func = base;
+            is_distinct[a] = 1;
+            has_distinct = true;
+            DistSet *ds = nullptr;
+            for (auto &d : dsets)
+                if (d.input_col == aggs[a].input_col) ds = &d;
+            if (!ds) {
+                dsets.emplace_back();
+                ds = &dsets.back();
+                ds->input_col = aggs[a].input_col;
+                ds->vtype = input_types[ds->input_col];
+                if (ds->vtype == GX_SLICE)
+                    ds->store.init(1, &ds->vtype, stream);
+            }
+            ds->agg_idx.push_back((int32_t)a);
+        }
         std::vector<int32_t> key_types;
         int width = 0;
         bool fixed = true;
@@ -617,6 +833,9 @@ struct AggOp : gx_op {
          * directly (one random line/row). Memory = n_slots x stride x 8
          * (2x the group count at load 0.5), so gate on narrow state. */
         slot_records = stride <= 2 && cfg.n_group_cols > 0;
+        /* a distinct agg accumulates by gid from its own pass: state is
+         * gid-indexed (gids never move) */
+        if (has_distinct) slot_records = false;
     }
     ~AggOp() override {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -713,6 +932,113 @@ struct AggOp : gx_op {
         if (slot_records) d_records = std::move(new_records);
         n_slots = ns;
         mask = (uint32_t)(ns - 1);
+        return 0;
+    }
+
+    /* grow one distinct set's slot array to >= min_slots (pow2), migrating
+     * the owners */
+    int dist_grow(DistSet &ds, int64_t min_slots) {
+        int64_t ns = gx_pow2(std::max<int64_t>(min_slots, 2048));
+        if (ns <= ds.n_slots) return 0;
+        DevBuf fresh;
+        if (fresh.grow((size_t)ns * 8, stream)) return -1;
+        HIP_OK(hipMemsetAsync(fresh.p, 0, (size_t)ns * 8, stream));
+        if (ds.n_slots > 0 && ds.owners > 0)
+            hipLaunchKernelGGL(k_dist_rehash, dim3(gx_grid(ds.n_slots)),
+                               dim3(256), 0, stream,
+                               (const unsigned long long *)ds.d_slots.p,
+                               ds.n_slots, (unsigned long long *)fresh.p,
+                               (uint32_t)(ns - 1), (const DistRec *)ds.d_recs.p);
+        /* the rehash reads the old array: drain before it returns to the
+         * pool */
+        HIP_OK(hipStreamSynchronize(stream));
+        ds.d_slots = std::move(fresh);
+        ds.n_slots = ns;
+        return 0;
+    }
+
+    /* one chunk through one distinct set; the chunk's gids are final.
+     * An error return leaves the set half-updated (n_drows and the SLICE
+     * store already cover the chunk, its rows are unresolved): a failed
+     * consume poisons the op, as it does for the group table — close it. */
+    int distinct_pass(DistSet &ds, const StagedChunk &st, int64_t n,
+                      bool no_group_by) {
+        /* the claim word carries drow+1 in 32 bits — the group table's own
+         * row limit; fail, never wrap */
+        if (ds.n_drows + n >= 0xFFFFFFFFll) {
+            gx_set_err("DISTINCT set: more than 2^32-2 input rows");
+            return -1;
+        }
+        const int64_t base = ds.n_drows;
+        const DevColView in = st.views[ds.input_col];
+        if (ds.d_recs.grow((size_t)(base + n) * sizeof(DistRec), stream) ||
+            d_dstatus.grow((size_t)n, stream))
+            return -1;
+        if (!ds.d_ctl.p) {
+            if (ds.d_ctl.grow(8, stream)) return -1;
+            HIP_OK(hipMemsetAsync(ds.d_ctl.p, 0, 8, stream));
+        }
+        if (ds.vtype == GX_SLICE) {
+            gx_block vb = view_block(in);
+            gx_chunk vc;
+            vc.n_rows = (int32_t)n;
+            vc.n_blocks = 1;
+            vc.blocks = &vb;
+            if (ds.store.append(&vc)) return -1;
+        }
+        ds.n_drows = base + n;
+        hipLaunchKernelGGL(k_dist_pack, dim3(gx_grid(n)), dim3(256), 0, stream,
+                           in, n, base,
+                           no_group_by ? nullptr : (const uint32_t *)d_slotidx.p,
+                           (const AggSlot *)d_slots.p, (DistRec *)ds.d_recs.p,
+                           (uint8_t *)d_dstatus.p);
+        /* size by ACTUAL occupancy (+ headroom; the overflow retry covers
+         * the rest) — a chunk of duplicates must not buy a table sized for
+         * "every row is new". Small chunks reserve their worst case, as
+         * the group table does, so CHUNK_SIZE streams never retry. */
+        const int64_t headroom = n < (int64_t)(1 << 18) ? n : 1024;
+        int64_t want = ((int64_t)ds.owners + headroom) * 2;
+        if (ds.n_slots == 0) /* every group holds at least one pair */
+            want = std::max<int64_t>(want, cfg.expected_groups * 2);
+        if (dist_grow(ds, want)) return -1;
+
+        DistInsertParams IP;
+        std::memset(&IP, 0, sizeof(IP));
+        IP.vtype = ds.vtype;
+        IP.base_drow = base;
+        IP.n = n;
+        IP.status = (uint8_t *)d_dstatus.p;
+        IP.ctl = (uint32_t *)ds.d_ctl.p;
+        IP.A.n_aggs = (int32_t)ds.agg_idx.size();
+        IP.A.stride = stride;
+        IP.A.records = (unsigned long long *)d_records.p;
+        for (size_t k = 0; k < ds.agg_idx.size(); k++) {
+            const int32_t a = ds.agg_idx[k];
+            IP.A.func[k] = aggs[a].func;
+            IP.A.val_off[k] = val_off[a];
+            IP.A.seen_off[k] = seen_off[a];
+            IP.A.input[k] = in;
+        }
+        for (int attempt = 0;; attempt++) {
+            IP.slots = (unsigned long long *)ds.d_slots.p;
+            IP.mask = (uint32_t)(ds.n_slots - 1);
+            IP.recs = (const DistRec *)ds.d_recs.p;
+            if (ds.vtype == GX_SLICE) IP.store = ds.store.view(0);
+            hipLaunchKernelGGL(k_dist_insert, dim3(gx_grid(n)), dim3(256), 0,
+                               stream, IP);
+            uint32_t ctl[2] = {0, 0};
+            HIP_OK(hipMemcpyAsync(ctl, ds.d_ctl.p, 8, hipMemcpyDeviceToHost,
+                                  stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            ds.owners = ctl[1];
+            if (!ctl[0]) break;
+            if (attempt > 40) { gx_set_err("distinct set overflow loop"); return -1; }
+            HIP_OK(hipMemsetAsync(ds.d_ctl.p, 0, 4, stream));
+            /* x4, as the group table's overflow recovery */
+            if (dist_grow(ds, std::max<int64_t>(ds.n_slots * 4,
+                                                (int64_t)ds.owners * 4)))
+                return -1;
+        }
         return 0;
     }
 
@@ -879,19 +1205,25 @@ struct AggOp : gx_op {
             AP.base_krow = base_krow;
             AP.n = n;
             AP.global_group = (int)no_group_by;
-            AP.n_aggs = (int32_t)aggs.size();
             AP.stride = stride;
             AP.records = (unsigned long long *)d_records.p;
+            int32_t k = 0;
             for (size_t a = 0; a < aggs.size(); a++) {
-                AP.func[a] = aggs[a].func;
-                AP.val_off[a] = val_off[a];
-                AP.seen_off[a] = seen_off[a];
-                if (aggs[a].input_col >= 0) AP.input[a] = st.views[aggs[a].input_col];
-                else std::memset(&AP.input[a], 0, sizeof(DevColView));
+                if (is_distinct[a]) continue; /* fed by the distinct pass */
+                AP.func[k] = aggs[a].func;
+                AP.val_off[k] = val_off[a];
+                AP.seen_off[k] = seen_off[a];
+                if (aggs[a].input_col >= 0) AP.input[k] = st.views[aggs[a].input_col];
+                else std::memset(&AP.input[k], 0, sizeof(DevColView));
+                k++;
             }
-            hipLaunchKernelGGL(k_agg_accumulate, dim3(gx_grid(n)), dim3(256), 0,
-                               stream, AP);
+            AP.n_aggs = k;
+            if (k > 0 || !has_distinct)
+                hipLaunchKernelGGL(k_agg_accumulate, dim3(gx_grid(n)), dim3(256),
+                                   0, stream, AP);
         }
+        for (auto &ds : dsets)
+            if (distinct_pass(ds, st, n, no_group_by)) return -1;
         HIP_OK(hipEventRecord(ev1, stream));
         HIP_OK(hipStreamSynchronize(stream));
         {
@@ -973,6 +1305,34 @@ gx_op *gxop_agg_create(const gx_agg_cfg *cfg) {
     if (cfg)
         for (int32_t i = 0; i < cfg->n_aggs; i++) {
             int32_t f = cfg->aggs[i].func;
+            if (agg_distinct_base(f) >= 0) {
+                const int32_t col = cfg->aggs[i].input_col;
+                if (col < 0 || col >= cfg->n_input_cols) {
+                    gx_set_err("DISTINCT agg " + std::to_string(i) +
+                               ": input_col " + std::to_string(col) +
+                               " out of range");
+                    return nullptr;
+                }
+                const int32_t t = cfg->input_types[col];
+                const bool integral = t == GX_I64 || t == GX_I32;
+                bool ok;
+                switch (f) {
+                case GX_AGG_COUNT_DISTINCT:
+                    ok = integral || t == GX_F64 || t == GX_SLICE; break;
+                case GX_AGG_SUM_I64_DISTINCT: case GX_AGG_SUM_I64N_DISTINCT:
+                    ok = integral; break;
+                default: /* SUM_F64 / AVG_F64 convert integers */
+                    ok = integral || t == GX_F64; break;
+                }
+                if (!ok) {
+                    gx_set_err("DISTINCT agg " + std::to_string(i) +
+                               ": func " + std::to_string(f) +
+                               " does not take input type " +
+                               std::to_string(t));
+                    return nullptr;
+                }
+                continue;
+            }
             if ((f < GX_AGG_COUNT_ROW || f > GX_AGG_BIT_XOR) &&
                 f != GX_AGG_SUM_I64N) {
                 gx_set_err("unknown or window-only agg func in group-by");

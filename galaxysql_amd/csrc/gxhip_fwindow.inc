@@ -909,6 +909,11 @@ gx_op *gxop_fwindow_create(const gx_fwindow_cfg *cfg) {
     }
     for (int32_t i = 0; i < cfg->n_frames; i++) {
         const gx_frame_spec &f = cfg->frames[i];
+        if (gx_agg_is_distinct(f.func)) {
+            gx_set_err("DISTINCT aggregates are gxop_agg only "
+                       "(not supported in frame-window)");
+            return nullptr;
+        }
         if (f.func == GX_AGG_RANK || f.func == GX_AGG_DENSE_RANK) {
             gx_set_err("RANK/DENSE_RANK are window-only");
             return nullptr;

@@ -645,6 +645,11 @@ gx_op *gxop_window_create(const gx_window_cfg *cfg) {
     }
     for (int32_t i = 0; i < cfg->n_aggs; i++) {
         int32_t f = cfg->aggs[i].func;
+        if (gx_agg_is_distinct(f)) {
+            gx_set_err("DISTINCT aggregates are gxop_agg only "
+                       "(not supported in window)");
+            return nullptr;
+        }
         /* running window: accumulators + rank family + null-init Sum;
          * navigation/distribution funcs are frame-window only */
         if ((f < GX_AGG_COUNT_ROW || f > GX_AGG_DENSE_RANK) &&

@@ -121,6 +121,12 @@ def final_agg_specs(n_group_cols, aggs):
     out_types = []
     for i, (func, _col) in enumerate(aggs):
         col = n_group_cols + i
+        if func in abi.DISTINCT_FUNCS:
+            raise ValueError(
+                f"DISTINCT agg func {func} cannot be split partial->final: "
+                "a value seen on two ranks would count twice. Shuffle the "
+                "rows by the group keys, then aggregate in a single phase "
+                "on the owning rank")
         if func == abi.AVG_F64:
             raise ValueError(
                 "AVG must be planned as partial SUM+COUNT around an "

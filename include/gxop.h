@@ -260,7 +260,7 @@ typedef enum gx_agg_func {
     GX_AGG_NTILE       = 19, /* MySQL split: first size%n buckets get +1 */
     GX_AGG_CUME_DIST   = 20, /* rows <= current ORDER run / partition size */
     GX_AGG_PERCENT_RANK = 21,/* (rank-1) / (partition size-1); 0 if size 1 */
-    GX_AGG_SUM_I64N  = 22  /* SQL SUM over integers, NULL-init (the Sum /
+    GX_AGG_SUM_I64N  = 22, /* SQL SUM over integers, NULL-init (the Sum /
                               Long2DecimalSum family AggregateUtils maps
                               SqlKind.SUM to, AggregateUtils.java:175-197):
                               an empty or all-NULL group/frame emits NULL,
@@ -268,6 +268,38 @@ typedef enum gx_agg_func {
                               init 0). The window frame classes use the
                               same null-init Sum (OverWindowFramesExecTest
                               fixtures). */
+    /* DISTINCT aggregates — the named class constructed with
+     * isDistinct=true (AggregateUtils.convertAggregators,
+     * AggregateUtils.java:133-213). AggOpenHashMap.putChunk asks a
+     * per-aggregator DistinctSet, a GroupOpenHashMap over (groupId, value),
+     * whether the pair was seen and accumulates only when it was not
+     * (AggOpenHashMap.java:100-139, operator/util/DistinctSet.java). So:
+     * the set is per (group, input column); a value counts once per group
+     * however many rows and consume calls carry it; NULL inputs never
+     * accumulate; value hash and equality are those of a group-key column
+     * of the same type (F64: IEEE ==, so NaN never equals NaN; -0.0 and
+     * +0.0 compare equal but hash apart, in the reference too, so whether
+     * they merge depends on table layout — keep them out of parity tests).
+     * gxop_agg_create ONLY (grouped and global); the group-join, window
+     * and frame-window creates reject these. Inputs: I64/I32 for the
+     * integer sums, I64/I32/F64 for the F64 sums (integers convert, as for
+     * the base funcs), and additionally SLICE for COUNT_DISTINCT.
+     * Not separate funcs, by design:
+     *  - MIN/MAX/BIT_AND/BIT_OR DISTINCT are the plain funcs (idempotent);
+     *    the caller maps them.
+     *  - BIT_XOR DISTINCT is plain BIT_XOR: the reference's BitXor
+     *    constructors take no distinct flag (AggregateUtils.java:290-303).
+     *  - multi-column COUNT(DISTINCT a, b) and CountRow with distinct are
+     *    not supported; such plans stay on the CPU.
+     *  - per-aggregator FILTER is not part of this ABI. */
+    GX_AGG_COUNT_DISTINCT    = 23, /* Count (single column): BIGINT, never
+                                      NULL; 0 when no non-null input */
+    GX_AGG_SUM_I64_DISTINCT  = 24, /* Long2LongSum0: BIGINT, init 0 */
+    GX_AGG_SUM_I64N_DISTINCT = 25, /* Sum / Long2DecimalSum family: BIGINT,
+                                      NULL when no non-null input */
+    GX_AGG_SUM_F64_DISTINCT  = 26, /* Double2DoubleSum: DOUBLE, init NULL */
+    GX_AGG_AVG_F64_DISTINCT  = 27  /* Avg over doubles: state {sum, count}
+                                      over the distinct values, init NULL */
 } gx_agg_func;
 
 typedef struct gx_agg_spec {
