@@ -341,6 +341,13 @@ class GxLib:
         L.gxop_scan_consume.argtypes = [C.c_void_p, C.POINTER(GxChunk),
                                         C.POINTER(C.POINTER(GxResult))]
         L.gxop_scan_close.argtypes = [C.c_void_p]
+        # fused scan+probe: HIP library only (the oracle does not export
+        # it) — callers test has_probe_scan
+        self.has_probe_scan = hasattr(L, "gxop_join_probe_scan")
+        if self.has_probe_scan:
+            L.gxop_join_probe_scan.argtypes = [
+                C.c_void_p, C.c_void_p, C.POINTER(GxChunk),
+                C.POINTER(C.POINTER(GxResult)), C.POINTER(C.c_int64)]
         L.gxop_result_copy_col.argtypes = [C.POINTER(GxResult), C.c_int32,
                                            C.c_void_p, C.c_void_p]
         L.gxop_join_get_stats.argtypes = [C.c_void_p, C.POINTER(GxJoinStats)]

@@ -819,8 +819,10 @@ __global__ void k_gather_multi(GatherParams G) {
                 }
                 continue;
             }
+            /* out_nulls NULL: the host proved the column null-free (source
+             * without nulls, index never the null marker) */
             bool nn = col_is_null(src, s);
-            G.out_nulls[c][i] = nn;
+            if (G.out_nulls[c]) G.out_nulls[c][i] = nn;
             switch (src.type) {
             case GX_I64: ((int64_t *)G.out_vals[c])[i] = nn ? 0 : ((const int64_t *)src.values)[s]; break;
             case GX_I32: ((int32_t *)G.out_vals[c])[i] = nn ? 0 : ((const int32_t *)src.values)[s]; break;
@@ -955,18 +957,21 @@ int ensure_device(int device) {
 /* Build a gx_result from exact-size device buffers. Each column owns a
  * values buf + nulls buf; SLICE columns use slot 0 for END-OFFSETS and a
  * data buf appended later by attach_slice_data (lengths known post-scan). */
-std::unique_ptr<HipResult> alloc_result_cols(const std::vector<int32_t> &types,
-                                             int64_t n, int device,
-                                             hipStream_t stream) {
+std::unique_ptr<HipResult> alloc_result_cols(
+    const std::vector<int32_t> &types, int64_t n, int device,
+    hipStream_t stream, const std::vector<uint8_t> *null_free = nullptr) {
     std::unique_ptr<HipResult> h(new HipResult());
     h->device = device;
     h->blocks.resize(types.size());
     h->bufs.resize(types.size() * 2);
     for (size_t c = 0; c < types.size(); c++) {
         size_t es = types[c] == GX_SLICE ? 4 : gx_fixed_size(types[c]);
+        /* a column the caller knows to be null-free gets no nulls buffer:
+         * its block's nulls stays NULL (gx_block: "may be NULL") */
+        const bool nf = null_free && (*null_free)[c];
         if (n > 0) {
             if (h->bufs[c * 2].grow((size_t)n * es, stream) ||
-                h->bufs[c * 2 + 1].grow((size_t)n, stream))
+                (!nf && h->bufs[c * 2 + 1].grow((size_t)n, stream)))
                 return nullptr;
         }
         gx_block &b = h->blocks[c];
@@ -1484,7 +1489,24 @@ struct JoinOp : gx_op {
                                            int64_t n_out) {
         std::vector<int32_t> otypes = output_types();
         if (otypes.size() > GX_MAX_COLS) { gx_set_err("too many output cols"); return nullptr; }
-        auto h = alloc_result_cols(otypes, n_out, device, stream);
+        /* an output column is null-free when its source column carries no
+         * nulls and its pair index is never the null marker: the probe
+         * index never is; the build index only in an INNER join (outer
+         * joins null-extend, SEMI/ANTI emit no build columns). Such a
+         * column gets no nulls buffer and no per-row null store. */
+        std::vector<uint8_t> null_free;
+        for (auto &spec : projected_specs()) {
+            const bool from_build = (spec.outer && cfg.build_outer) ||
+                                    (!spec.outer && !cfg.build_outer);
+            const DevColView src = from_build ? build.view(spec.src)
+                                              : probe.views[spec.src];
+            const bool idx_ok = from_build
+                ? (d_bpos != nullptr && cfg.join_type == GX_JOIN_INNER)
+                : d_pidx != nullptr;
+            null_free.push_back(idx_ok && !src.has_nulls &&
+                                src.type != GX_SLICE);
+        }
+        auto h = alloc_result_cols(otypes, n_out, device, stream, &null_free);
         if (!h || n_out == 0) return h;
 
         GatherParams G;
@@ -1952,11 +1974,13 @@ int gxop_result_to_host(gx_result *res) {
                                  hipMemcpyDeviceToHost));
             b.values = h->host.back().data();
         }
-        h->host.emplace_back((size_t)n);
-        if (n > 0)
-            HIP_OK(hipMemcpy(h->host.back().data(), (void *)b.nulls, (size_t)n,
-                             hipMemcpyDeviceToHost));
-        b.nulls = h->host.back().data();
+        if (b.nulls || n == 0) { /* NULL nulls = null-free column: stays NULL */
+            h->host.emplace_back((size_t)n);
+            if (n > 0)
+                HIP_OK(hipMemcpy(h->host.back().data(), (void *)b.nulls,
+                                 (size_t)n, hipMemcpyDeviceToHost));
+            b.nulls = h->host.back().data();
+        }
         b.mem = GX_MEM_HOST;
     }
     h->bufs.clear();

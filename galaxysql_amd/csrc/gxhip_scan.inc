@@ -13,16 +13,21 @@ namespace {
 
 #define GX_MAX_PREDS 8
 
-struct ScanParams {
-    int64_t n;
+/* predicate half of a scan: shared by k_scan and the fused probe-scan
+ * kernel, which takes it next to the join's ProbeParams */
+struct ScanPreds {
     int32_t n_preds;
-    int32_t pred_col[GX_MAX_PREDS];
     int32_t pred_cmp[GX_MAX_PREDS];
     int64_t pred_i64[GX_MAX_PREDS];
     double  pred_f64[GX_MAX_PREDS];
     const uint8_t *pred_pat[GX_MAX_PREDS];
     int32_t pred_plen[GX_MAX_PREDS];
     DevColView pred_view[GX_MAX_PREDS];
+};
+
+struct ScanParams {
+    int64_t n;
+    ScanPreds preds;
     int32_t n_projs;
     int32_t proj_op[GX_MAX_COLS];
     int32_t proj_scale[GX_MAX_COLS];
@@ -120,7 +125,7 @@ __device__ static inline bool cmp_f64(double a, int32_t cmp, double b) {
     }
 }
 
-__device__ static inline bool scan_row_passes(const ScanParams &P, int64_t i) {
+__device__ static inline bool scan_row_passes(const ScanPreds &P, int64_t i) {
     for (int p = 0; p < P.n_preds; p++) {
         const DevColView &c = P.pred_view[p];
         if (col_is_null(c, i)) return false; /* SQL: NULL fails */
@@ -157,6 +162,142 @@ __device__ static inline bool scan_row_passes(const ScanParams &P, int64_t i) {
     return true;
 }
 
+/* Evaluate one projection at source row `src` and store it at output row
+ * `at`. The one place a projected value is computed: k_scan and the fused
+ * probe-scan gather both call it, so their values are bit-identical. SLICE
+ * copies are not handled here (gathered in a post-pass). */
+__device__ static inline void proj_store(int32_t op, int32_t scale,
+                                         const DevColView &a,
+                                         const DevColView &b,
+                                         const DevColView &cc,
+                                         const DevColView &dd, int64_t src,
+                                         void *out_vals, uint8_t *out_nulls,
+                                         int64_t at, uint32_t *err) {
+    switch (op) {
+    case GX_PROJ_COPY: {
+        if (a.type == GX_SLICE) break; /* gathered post-pass */
+        bool nn = col_is_null(a, src);
+        if (out_nulls) out_nulls[at] = nn;
+        switch (a.type) {
+        case GX_I64: ((int64_t *)out_vals)[at] = nn ? 0 : ((const int64_t *)a.values)[src]; break;
+        case GX_I32: ((int32_t *)out_vals)[at] = nn ? 0 : ((const int32_t *)a.values)[src]; break;
+        case GX_F64: ((double *)out_vals)[at] = nn ? 0 : ((const double *)a.values)[src]; break;
+        case GX_DECIMAL:
+            for (int k = 0; k < 5; k++)
+                ((uint64_t *)out_vals)[(size_t)at * 5 + k] =
+                    nn ? 0 : ((const uint64_t *)a.values)[src * 5 + k];
+            break;
+        }
+        break; }
+    case GX_PROJ_DEC_TO_SCALED: {
+        bool nn = col_is_null(a, src);
+        if (out_nulls) out_nulls[at] = nn;
+        ((int64_t *)out_vals)[at] = nn ? 0
+            : dec40_to_scaled_dev((const uint8_t *)a.values +
+                                  (size_t)src * 40, scale, err);
+        break; }
+    case GX_PROJ_SCALED_TO_DEC: {
+        bool nn = col_is_null(a, src);
+        if (out_nulls) out_nulls[at] = nn;
+        uint8_t *dst = (uint8_t *)out_vals + (size_t)at * 40;
+        if (nn)
+            for (int k = 0; k < 5; k++) ((uint64_t *)dst)[k] = 0;
+        else
+            scaled_to_dec40_dev(((const int64_t *)a.values)[src], scale, dst);
+        break; }
+    case GX_PROJ_REV_F64: {
+        bool nn = col_is_null(a, src) || col_is_null(b, src);
+        if (out_nulls) out_nulls[at] = nn;
+        double av = nn ? 0 : ((const double *)a.values)[src];
+        double bv = nn ? 0 : ((const double *)b.values)[src];
+        ((double *)out_vals)[at] = av * (1.0 - bv);
+        break; }
+    case GX_PROJ_REV_SCALED4: {
+        bool nn = col_is_null(a, src) || col_is_null(b, src);
+        if (out_nulls) out_nulls[at] = nn;
+        int64_t av = nn ? 0 : ((const int64_t *)a.values)[src];
+        int64_t bv = nn ? 0 : ((const int64_t *)b.values)[src];
+        ((int64_t *)out_vals)[at] =
+            (int64_t)((uint64_t)av * (uint64_t)(100 - bv));
+        break; }
+    case GX_PROJ_Q9_AMOUNT4: {
+        bool nn = col_is_null(a, src) || col_is_null(b, src) ||
+                  col_is_null(cc, src) || col_is_null(dd, src);
+        if (out_nulls) out_nulls[at] = nn;
+        int64_t av = nn ? 0 : ((const int64_t *)a.values)[src];
+        int64_t bv = nn ? 0 : ((const int64_t *)b.values)[src];
+        int64_t cv = nn ? 0 : ((const int64_t *)cc.values)[src];
+        int64_t dv = nn ? 0 : ((const int64_t *)dd.values)[src];
+        ((int64_t *)out_vals)[at] =
+            (int64_t)((uint64_t)av * (uint64_t)(100 - bv)) -
+            (int64_t)((uint64_t)cv * (uint64_t)dv * 100u);
+        break; }
+    }
+}
+
+/* Fused scan + probe (gxop_join_probe_scan fast path): k_probe with a
+ * predicate stage in front. Grid-strides over the RAW rows; a lane whose
+ * row fails the scan predicates is inactive for probe_one (its NULL-key
+ * test, bloom test, bucket walk and emit staging are unchanged and stay
+ * wave-synchronous), so the emitted probe index is the raw row id and no
+ * projected column is materialized for rows the join drops. Survivors of
+ * the predicates are counted per wave in a register (one ballot/popcount
+ * per iteration) and added to *kept once per wave. */
+__global__ void k_probe_scan(ProbeParams P, ScanPreds S, uint32_t *kept) {
+    __shared__ uint32_t s_pairs[2][4][GX_EMIT_STAGE]; /* [p/b][wave][slot] */
+    EmitStage E;
+    {
+        int wid = threadIdx.x >> 6;
+        E.s_p = s_pairs[0][wid];
+        E.s_b = s_pairs[1][wid];
+        E.cnt = 0;
+        E.lane = threadIdx.x & 63;
+    }
+    uint32_t n_kept = 0; /* wave-uniform */
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t base = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;;
+         base += stride) {
+        bool in = base < P.n_probe;
+        if (!__ballot(in)) break;
+        bool pass = in && scan_row_passes(S, base);
+        n_kept += (uint32_t)__popcll(__ballot(pass));
+        probe_one(P, E, pass, base);
+    }
+    emit_flush(P, E);
+    if (E.lane == 0 && n_kept) atomicAdd(kept, n_kept);
+}
+
+/* Materialize the fused probe's pair list: probe-side output columns are
+ * the scan's projections evaluated at the raw row id (side 0), build-side
+ * columns are plain gathers at the build position (side 1, a COPY). */
+struct ProjGatherParams {
+    const uint32_t *pidx;
+    const uint32_t *bidx;
+    int64_t n;
+    int32_t n_cols;
+    int32_t side[GX_MAX_COLS];
+    int32_t op[GX_MAX_COLS];
+    int32_t scale[GX_MAX_COLS];
+    DevColView a[GX_MAX_COLS];
+    DevColView b[GX_MAX_COLS];
+    DevColView c[GX_MAX_COLS];
+    DevColView d[GX_MAX_COLS];
+    void *out_vals[GX_MAX_COLS];
+    uint8_t *out_nulls[GX_MAX_COLS];
+};
+
+__global__ void k_gather_proj(ProjGatherParams G) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < G.n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t pi = G.pidx[i];
+        const int64_t bi = G.bidx[i];
+        for (int c = 0; c < G.n_cols; c++)
+            proj_store(G.op[c], G.scale[c], G.a[c], G.b[c], G.c[c], G.d[c],
+                       G.side[c] ? bi : pi, G.out_vals[c], G.out_nulls[c], i,
+                       nullptr);
+    }
+}
+
 __global__ void k_scan(ScanParams P) {
     /* per-wave LDS staging of surviving row indices, then each flush
      * writes the projected columns coalesced (same batching rationale as
@@ -177,76 +318,10 @@ __global__ void k_scan(ScanParams P) {
             if (at >= P.cap) continue;
             int64_t src = stage[k];
             if (P.out_rowids) P.out_rowids[at] = (uint32_t)src;
-            for (int c = 0; c < P.n_projs; c++) {
-                const DevColView &a = P.proj_a[c];
-                switch (P.proj_op[c]) {
-                case GX_PROJ_COPY: {
-                    if (a.type == GX_SLICE) break; /* gathered post-pass */
-                    bool nn = col_is_null(a, src);
-                    P.out_nulls[c][at] = nn;
-                    switch (a.type) {
-                    case GX_I64: ((int64_t *)P.out_vals[c])[at] = nn ? 0 : ((const int64_t *)a.values)[src]; break;
-                    case GX_I32: ((int32_t *)P.out_vals[c])[at] = nn ? 0 : ((const int32_t *)a.values)[src]; break;
-                    case GX_F64: ((double *)P.out_vals[c])[at] = nn ? 0 : ((const double *)a.values)[src]; break;
-                    case GX_DECIMAL:
-                        for (int k = 0; k < 5; k++)
-                            ((uint64_t *)P.out_vals[c])[(size_t)at * 5 + k] =
-                                nn ? 0 : ((const uint64_t *)a.values)[src * 5 + k];
-                        break;
-                    }
-                    break; }
-                case GX_PROJ_DEC_TO_SCALED: {
-                    bool nn = col_is_null(a, src);
-                    P.out_nulls[c][at] = nn;
-                    ((int64_t *)P.out_vals[c])[at] = nn ? 0
-                        : dec40_to_scaled_dev((const uint8_t *)a.values +
-                                              (size_t)src * 40,
-                                              P.proj_scale[c], P.err);
-                    break; }
-                case GX_PROJ_SCALED_TO_DEC: {
-                    bool nn = col_is_null(a, src);
-                    P.out_nulls[c][at] = nn;
-                    uint8_t *dst = (uint8_t *)P.out_vals[c] + (size_t)at * 40;
-                    if (nn)
-                        for (int k = 0; k < 5; k++) ((uint64_t *)dst)[k] = 0;
-                    else
-                        scaled_to_dec40_dev(((const int64_t *)a.values)[src],
-                                            P.proj_scale[c], dst);
-                    break; }
-                case GX_PROJ_REV_F64: {
-                    const DevColView &b = P.proj_b[c];
-                    bool nn = col_is_null(a, src) || col_is_null(b, src);
-                    P.out_nulls[c][at] = nn;
-                    double av = nn ? 0 : ((const double *)a.values)[src];
-                    double bv = nn ? 0 : ((const double *)b.values)[src];
-                    ((double *)P.out_vals[c])[at] = av * (1.0 - bv);
-                    break; }
-                case GX_PROJ_REV_SCALED4: {
-                    const DevColView &b = P.proj_b[c];
-                    bool nn = col_is_null(a, src) || col_is_null(b, src);
-                    P.out_nulls[c][at] = nn;
-                    int64_t av = nn ? 0 : ((const int64_t *)a.values)[src];
-                    int64_t bv = nn ? 0 : ((const int64_t *)b.values)[src];
-                    ((int64_t *)P.out_vals[c])[at] =
-                        (int64_t)((uint64_t)av * (uint64_t)(100 - bv));
-                    break; }
-                case GX_PROJ_Q9_AMOUNT4: {
-                    const DevColView &b = P.proj_b[c];
-                    const DevColView &cc = P.proj_c[c];
-                    const DevColView &dd = P.proj_d[c];
-                    bool nn = col_is_null(a, src) || col_is_null(b, src) ||
-                              col_is_null(cc, src) || col_is_null(dd, src);
-                    P.out_nulls[c][at] = nn;
-                    int64_t av = nn ? 0 : ((const int64_t *)a.values)[src];
-                    int64_t bv = nn ? 0 : ((const int64_t *)b.values)[src];
-                    int64_t cv = nn ? 0 : ((const int64_t *)cc.values)[src];
-                    int64_t dv = nn ? 0 : ((const int64_t *)dd.values)[src];
-                    ((int64_t *)P.out_vals[c])[at] =
-                        (int64_t)((uint64_t)av * (uint64_t)(100 - bv)) -
-                        (int64_t)((uint64_t)cv * (uint64_t)dv * 100u);
-                    break; }
-                }
-            }
+            for (int c = 0; c < P.n_projs; c++)
+                proj_store(P.proj_op[c], P.proj_scale[c], P.proj_a[c],
+                           P.proj_b[c], P.proj_c[c], P.proj_d[c], src,
+                           P.out_vals[c], P.out_nulls[c], at, P.err);
         }
         cnt = 0;
     };
@@ -256,7 +331,7 @@ __global__ void k_scan(ScanParams P) {
          base_i += stride) {
         bool active = base_i < P.n;
         if (!__ballot(active)) break;
-        bool want = active && scan_row_passes(P, base_i);
+        bool want = active && scan_row_passes(P.preds, base_i);
         unsigned long long m = __ballot(want);
         uint32_t add = (uint32_t)__popcll(m);
         if (cnt + add > GX_EMIT_STAGE) flush();
@@ -307,6 +382,37 @@ struct ScanOp : gx_op {
         return 0;
     }
 
+    /* predicate constants + the staged chunk's predicate columns */
+    int fill_preds(ScanPreds &S, const StagedChunk &st) {
+        std::memset(&S, 0, sizeof(S));
+        if (upload_patterns()) return -1;
+        S.n_preds = (int32_t)preds.size();
+        for (size_t p = 0; p < preds.size(); p++) {
+            S.pred_cmp[p] = preds[p].cmp;
+            S.pred_i64[p] = preds[p].v_i64;
+            S.pred_f64[p] = preds[p].v_f64;
+            S.pred_pat[p] = (const uint8_t *)d_pats[p].p;
+            S.pred_plen[p] = preds[p].v_len;
+            S.pred_view[p] = st.views[preds[p].col];
+        }
+        return 0;
+    }
+
+    /* projection p's output is null-free when none of the raw columns it
+     * reads carries nulls (SLICE outputs keep their nulls: the slice
+     * gather writes them) */
+    bool proj_null_free(size_t p, const StagedChunk &st) const {
+        const gx_proj &pr = projs[p];
+        if (out_types[p] == GX_SLICE) return false;
+        bool nf = !st.views[pr.a].has_nulls;
+        if (pr.op == GX_PROJ_REV_F64 || pr.op == GX_PROJ_REV_SCALED4 ||
+            pr.op == GX_PROJ_Q9_AMOUNT4)
+            nf = nf && !st.views[pr.b].has_nulls;
+        if (pr.op == GX_PROJ_Q9_AMOUNT4)
+            nf = nf && !st.views[pr.c].has_nulls && !st.views[pr.d].has_nulls;
+        return nf;
+    }
+
     int consume(const gx_chunk *ch, gx_result **out) {
         *out = nullptr;
         if (ensure_device(device)) return -1;
@@ -317,23 +423,16 @@ struct ScanOp : gx_op {
         /* pass 1 would count; instead allocate full-capacity output and
          * shrink by the counter (filters keep a bounded fraction and
          * the buffers come from the pool) */
-        auto h = alloc_result_cols(out_types, n, device, stream);
+        std::vector<uint8_t> null_free;
+        for (size_t c = 0; c < projs.size(); c++)
+            null_free.push_back(proj_null_free(c, st));
+        auto h = alloc_result_cols(out_types, n, device, stream, &null_free);
         if (!h) return -1;
         HIP_OK(hipMemsetAsync(d_meta.p, 0, 8, stream));
         ScanParams P;
         std::memset(&P, 0, sizeof(P));
         P.n = n;
-        P.n_preds = (int32_t)preds.size();
-        if (upload_patterns()) return -1;
-        for (size_t p = 0; p < preds.size(); p++) {
-            P.pred_col[p] = preds[p].col;
-            P.pred_cmp[p] = preds[p].cmp;
-            P.pred_i64[p] = preds[p].v_i64;
-            P.pred_f64[p] = preds[p].v_f64;
-            P.pred_pat[p] = (const uint8_t *)d_pats[p].p;
-            P.pred_plen[p] = preds[p].v_len;
-            P.pred_view[p] = st.views[preds[p].col];
-        }
+        if (fill_preds(P.preds, st)) return -1;
         P.n_projs = (int32_t)projs.size();
         for (size_t c = 0; c < projs.size(); c++) {
             P.proj_op[c] = projs[c].op;
@@ -390,9 +489,198 @@ struct ScanOp : gx_op {
     }
 };
 
+/* ---- fused scan + probe (gxop_join_probe_scan) ------------------------ */
+
+/* The fast path's conditions (gxop.h): fast_i64 inline-bucket table, plain
+ * INNER/SEMI equi-join, probe key = COPY of a raw I64 column, no SLICE
+ * anywhere on the output, no DEC_TO_SCALED projection (its wide-DECIMAL
+ * fence must fire for every surviving row; late evaluation would only see
+ * the matched ones), device-resident input. Anything else runs the
+ * composed scan -> probe sequence. */
+bool probe_scan_fast_ok(const JoinOp *j, const ScanOp *s,
+                        const gx_chunk *raw) {
+    if (!j->built || !j->fast_i64 || j->pass_nothing || j->pass_through)
+        return false;
+    const gx_join_cfg &c = j->cfg;
+    if (c.build_outer || c.single_join || !j->conds.empty()) return false;
+    if (c.join_type != GX_JOIN_INNER && c.join_type != GX_JOIN_SEMI)
+        return false;
+    if (raw->n_rows <= 0 || raw->n_blocks != (int32_t)s->input_types.size())
+        return false;
+    for (int32_t b = 0; b < raw->n_blocks; b++)
+        if (raw->blocks[b].mem != GX_MEM_DEVICE) return false;
+    const gx_proj &kp = s->projs[(size_t)j->probe_key_cols[0]];
+    if (kp.op != GX_PROJ_COPY || s->input_types[kp.a] != GX_I64) return false;
+    for (size_t p = 0; p < s->projs.size(); p++)
+        if (s->projs[p].op == GX_PROJ_DEC_TO_SCALED ||
+            s->out_types[p] == GX_SLICE)
+            return false;
+    std::vector<JoinOp::OutSpec> specs = j->projected_specs();
+    if (specs.size() > GX_MAX_COLS) return false;
+    for (auto &sp : specs)
+        if (sp.type == GX_SLICE) return false;
+    return true;
+}
+
+int probe_scan_fused(JoinOp *j, ScanOp *s, const gx_chunk *raw,
+                     gx_result **out, int64_t *n_kept) {
+    if (ensure_device(j->device)) return -1;
+    hipStream_t stream = j->stream;
+    StagedChunk st;
+    if (st.stage(raw, stream)) return -1; /* device-resident: zero copy */
+    const int64_t n = st.n_rows;
+    ScanPreds S;
+    if (s->fill_preds(S, st)) return -1;
+    const gx_proj &kp = s->projs[(size_t)j->probe_key_cols[0]];
+
+    /* first attempt sized like gxop_join_probe's, on the raw row count */
+    uint32_t cap = (uint32_t)std::min<int64_t>(
+        std::max<int64_t>((int64_t)n * 2, 1 << 16), INT64_C(1) << 31);
+    if (j->d_meta.grow(16, stream)) return -1;
+    for (int attempt = 0; attempt < 4; attempt++) {
+        if (j->d_pidx.grow((size_t)cap * 4, stream) ||
+            j->d_bpos.grow((size_t)cap * 4, stream)) return -1;
+        HIP_OK(hipMemsetAsync(j->d_meta.p, 0, 16, stream));
+        ProbeParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.table = (const JoinEntry *)j->d_table.p;
+        P.entries = (const JoinEntry *)j->d_entries.p;
+        P.mask = j->mask;
+        P.n_probe = n;
+        P.bloom = (const uint32_t *)j->d_bloom.p;
+        P.bloom_mask = j->bloom_mask;
+        P.fast_i64 = 1;
+        P.build_keys = j->key_views(j->build, j->build_key_cols);
+        P.probe_keys.n = 1;
+        P.probe_keys.col[0] = st.views[kp.a];
+        P.join_type = j->cfg.join_type;
+        P.semi_join = j->cfg.join_type == GX_JOIN_SEMI;
+        P.anti_null_col = -1;
+        P.out_probe = (uint32_t *)j->d_pidx.p;
+        P.out_build = (uint32_t *)j->d_bpos.p;
+        P.cap = cap;
+        P.counter = (uint32_t *)j->d_meta.p;
+        P.err = (uint32_t *)j->d_meta.p + 1;
+        if (!j->ev0) {
+            HIP_OK(hipEventCreate(&j->ev0));
+            HIP_OK(hipEventCreate(&j->ev1));
+        }
+        HIP_OK(hipEventRecord(j->ev0, stream));
+        hipLaunchKernelGGL(k_probe_scan, dim3(gx_grid(n)), dim3(256), 0,
+                           stream, P, S, (uint32_t *)j->d_meta.p + 2);
+        HIP_OK(hipEventRecord(j->ev1, stream));
+        uint32_t meta[3];
+        HIP_OK(hipMemcpyAsync(meta, j->d_meta.p, 12, hipMemcpyDeviceToHost,
+                              stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        {
+            float ms = 0;
+            HIP_OK(hipEventElapsedTime(&ms, j->ev0, j->ev1));
+            j->probe_kernel_ms += ms;
+            j->probe_launches++;
+        }
+        if (meta[0] > cap) { cap = meta[0]; continue; } /* exact-size retry */
+
+        const int64_t n_out = meta[0];
+        j->probe_rows_total += meta[2];
+        j->matches_total += n_out;
+        *n_kept = meta[2];
+        std::vector<JoinOp::OutSpec> specs = j->projected_specs();
+        std::vector<int32_t> otypes;
+        std::vector<uint8_t> null_free; /* as in the scan and the join */
+        for (auto &sp : specs) {
+            otypes.push_back(sp.type);
+            null_free.push_back(sp.outer
+                ? s->proj_null_free((size_t)sp.src, st)
+                : !j->build.view(sp.src).has_nulls);
+        }
+        auto h = alloc_result_cols(otypes, n_out, j->device, stream,
+                                   &null_free);
+        if (!h) return -1;
+        if (n_out > 0) {
+            ProjGatherParams G;
+            std::memset(&G, 0, sizeof(G));
+            G.pidx = (const uint32_t *)j->d_pidx.p;
+            G.bidx = (const uint32_t *)j->d_bpos.p;
+            G.n = n_out;
+            G.n_cols = (int32_t)specs.size();
+            for (size_t c = 0; c < specs.size(); c++) {
+                G.out_vals[c] = h->bufs[c * 2].p;
+                G.out_nulls[c] = (uint8_t *)h->bufs[c * 2 + 1].p;
+                if (!specs[c].outer) { /* build side: plain gather */
+                    G.side[c] = 1;
+                    G.op[c] = GX_PROJ_COPY;
+                    G.a[c] = j->build.view(specs[c].src);
+                    continue;
+                }
+                const gx_proj &pr = s->projs[(size_t)specs[c].src];
+                G.side[c] = 0;
+                G.op[c] = pr.op;
+                G.a[c] = st.views[pr.a];
+                if (pr.op == GX_PROJ_SCALED_TO_DEC)
+                    G.scale[c] = pr.c;   /* c = scale, not a col */
+                else if (pr.op != GX_PROJ_COPY)
+                    G.b[c] = st.views[pr.b];
+                if (pr.op == GX_PROJ_Q9_AMOUNT4) {
+                    G.c[c] = st.views[pr.c];
+                    G.d[c] = st.views[pr.d];
+                }
+            }
+            hipLaunchKernelGGL(k_gather_proj, dim3(gx_grid(n_out)), dim3(256),
+                               0, stream, G);
+            /* the pair lists are reused by the next probe: drain first */
+            HIP_OK(hipStreamSynchronize(stream));
+        }
+        give_result(std::move(h), out);
+        return 0;
+    }
+    return -1; /* pair list still short after 4 resizes */
+}
+
 } // namespace
 
 extern "C" {
+
+int gxop_join_probe_scan(gx_op *join, gx_op *scan, const gx_chunk *raw_chunk,
+                         gx_result **out, int64_t *n_scan_kept) {
+    if (!join || join->kind != OP_JOIN) { gx_set_err("not a join op"); return -1; }
+    if (!scan || scan->kind != OP_SCAN) { gx_set_err("not a scan op"); return -1; }
+    if (!raw_chunk || !out) { gx_set_err("probe_scan: null argument"); return -1; }
+    *out = nullptr;
+    if (join->device != scan->device || join->stream != scan->stream) {
+        gx_set_err("probe_scan: join and scan must share device and stream");
+        return -1;
+    }
+    ScanOp *s = static_cast<ScanOp *>(scan);
+    std::lock_guard<std::mutex> lk(join->mu);
+    JoinOp *j = join->variant == 0 ? static_cast<JoinOp *>(join) : nullptr;
+    HybridJoinOp *hj = j ? nullptr : static_cast<HybridJoinOp *>(join);
+    const gx_join_cfg &cfg = j ? j->cfg : hj->cfg;
+    const std::vector<int32_t> &pt = cfg.build_outer
+        ? (j ? j->inner_types : hj->inner_types)
+        : (j ? j->outer_types : hj->outer_types);
+    if (pt != s->out_types) {
+        gx_set_err("probe_scan: scan's projected types differ from the "
+                   "join's probe-side types");
+        return -1;
+    }
+    if (!(j ? j->built : hj->built)) { gx_set_err("probe before build"); return -1; }
+    int64_t kept = 0;
+    int rc;
+    if (j && probe_scan_fast_ok(j, s, raw_chunk)) {
+        rc = probe_scan_fused(j, s, raw_chunk, out, &kept);
+    } else {
+        /* composed sequence: scan, then probe with its projected chunk */
+        gx_result *t = nullptr;
+        rc = s->consume(raw_chunk, &t);
+        if (rc) return rc;
+        kept = t->chunk.n_rows;
+        rc = j ? j->probe(&t->chunk, out) : hj->probe(&t->chunk, out);
+        gxop_result_release(t);
+    }
+    if (rc == 0 && n_scan_kept) *n_scan_kept = kept;
+    return rc;
+}
 
 gx_op *gxop_scan_create(const gx_scan_cfg *cfg) {
     if (!cfg || cfg->n_preds > GX_MAX_PREDS || cfg->n_projs > GX_MAX_COLS ||

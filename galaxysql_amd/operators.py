@@ -120,6 +120,18 @@ class ParallelHashJoinExec:
             return None
         return self._lib.result_to_chunk(out)
 
+    def probe_scan(self, scan, chunk_ref):
+        """Fused scan+probe (gxop_join_probe_scan): probe with the rows of
+        the raw chunk (a byref'd GxChunk) that pass `scan`'s predicates.
+        Returns (gx_result pointer or None, rows that passed the scan).
+        Only on a library with has_probe_scan."""
+        out = C.POINTER(GxResult)()
+        kept = C.c_int64(0)
+        self._lib.check(self._lib.lib.gxop_join_probe_scan(
+            self._op, scan._op, chunk_ref, C.byref(out), C.byref(kept)),
+            "join_probe_scan")
+        return (out if out else None), kept.value
+
     def probe_push(self, chunk: Chunk):
         """Buffered probe (gxop.h: the LocalBufferExec pattern): stage a
         chunk device-side without launching kernels."""

@@ -57,7 +57,21 @@ def _consume_src(lib, op, src, types):
                   "join_consume")
 
 
+class _ScanSrc:
+    """A probe input that is still an unscanned table: the scan op plus the
+    raw chunk it would consume. _probe_src feeds it to the join through the
+    fused gxop_join_probe_scan and records how many rows passed the scan."""
+
+    def __init__(self, scan, chunk):
+        self.scan = scan
+        self.chunk = chunk
+        self.kept = 0
+
+
 def _probe_src(lib, op, src, types):
+    if isinstance(src, _ScanSrc):
+        out, src.kept = op.probe_scan(src.scan, C.byref(src.chunk))
+        return out
     if isinstance(src, list):
         return _probe_tensors(lib, op, src, types)
     out = C.POINTER(GxResult)()
@@ -252,10 +266,28 @@ def run_q3_honest(lib, device, raw_cust, raw_orders, raw_lineitem,
         ka = []
         rc = sc.consume_raw(C.byref(chunk_from_torch(lib, list(raw_cust),
                                                      RAW_CUST_TYPES, ka)))
-        ro = so.consume_raw(C.byref(chunk_from_torch(lib, list(raw_orders),
-                                                     RAW_ORDERS_TYPES, ka)))
-        rl = sl.consume_raw(C.byref(chunk_from_torch(lib, list(raw_lineitem),
-                                                     RAW_LINEITEM_TYPES, ka)))
+        ch_o = chunk_from_torch(lib, list(raw_orders), RAW_ORDERS_TYPES, ka)
+        ch_l = chunk_from_torch(lib, list(raw_lineitem), RAW_LINEITEM_TYPES,
+                                ka)
+        # Single-GPU chain on a library with the fused entry: orders and
+        # lineitem are the PROBE sides of join1/join2, so they go to the
+        # joins unscanned (predicate + probe in one kernel, projections
+        # evaluated only for matched rows). customer is a build side and
+        # the N>1 path needs the scan outputs for the shuffle: plain scans.
+        fused = not as_tensors and getattr(lib, "has_probe_scan", False)
+        if fused:
+            src_o = _ScanSrc(so, ch_o)
+            src_l = _ScanSrc(sl, ch_l)
+            chunks, info = run_q3(lib, device, rc, src_o, src_l,
+                                  expected_groups=expected_groups,
+                                  to_host=to_host, local_rank=local_rank,
+                                  keep_results=keep_results)
+            info.update({"cust_kept": rc.contents.chunk.n_rows if rc else 0,
+                         "orders_kept_scan": src_o.kept,
+                         "lineitem_kept": src_l.kept})
+            return chunks, info
+        ro = so.consume_raw(C.byref(ch_o))
+        rl = sl.consume_raw(C.byref(ch_l))
         scanned = {"cust_kept": rc.contents.chunk.n_rows if rc else 0,
                    "orders_kept_scan": ro.contents.chunk.n_rows if ro else 0,
                    "lineitem_kept": rl.contents.chunk.n_rows if rl else 0}

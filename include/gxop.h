@@ -84,7 +84,10 @@ typedef struct gx_chunk {
 
 /* An output batch owned by the library; free with gxop_result_release.
  * Blocks' mem tells where the data lives; gxop_result_to_host() copies a
- * device-resident result into host memory in place. */
+ * device-resident result into host memory in place. As for input blocks,
+ * a result block's nulls may be NULL: scan and join outputs leave it NULL
+ * for a column whose source columns arrived without nulls and which the
+ * join cannot null-extend. */
 typedef struct gx_result {
     gx_chunk chunk;
     void    *opaque;
@@ -635,4 +638,10 @@ int gxop_abi_version(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* Everything above is exported by BOTH libraries (the HIP product and the
+ * CPU oracle). Entry points only the HIP library exports — the fused
+ * scan+probe — are declared in gxop_hip.h; callers test for the symbol. */
+#include "gxop_hip.h"
+
 #endif /* GXOP_H */
