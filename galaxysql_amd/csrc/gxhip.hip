@@ -300,7 +300,8 @@ __global__ void k_any_null(DevColView c, int64_t n, uint32_t *flag) {
  * on 64-B lines fetched per 16-B entry; this layout removes the whole
  * starts[] indirection. Overflow (count > 4, ~0.4% of buckets at load 1)
  * continues into entries[ovf_start ..]. e[0] is loaded unconditionally
- * (count rides in it); e[1..3] load lazily from the same line.
+ * (count rides in it); e[1..3] load lazily from the same line. The build
+ * (k_join_insert below) fills it in one pass over the build rows.
  *
  * CSR (null_safe_keys group-join builds only): starts[b]..starts[b+1]
  * index a contiguous entries[] run — kept because the group-join kernels
@@ -353,76 +354,165 @@ __device__ static inline uint64_t bloom_mix(int64_t key) {
     return x;
 }
 
-/* line_mask = (n_lines - 1); lines of 16 u32 words (64 B) */
-__global__ void k_bloom_set(DevColView key0, int64_t n, uint32_t *bloom,
-                            uint32_t line_mask) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        if (col_is_null(key0, i)) continue;
-        uint64_t x = bloom_mix(((const int64_t *)key0.values)[i]);
-        uint32_t *line = bloom + ((uint32_t)x & line_mask) * 16;
-        uint32_t b1 = (uint32_t)(x >> 32) & 511u;
-        uint32_t b2 = (uint32_t)(x >> 41) & 511u;
-        atomicOr(&line[b1 >> 5], 1u << (b1 & 31));
-        atomicOr(&line[b2 >> 5], 1u << (b2 & 31));
-    }
+/* Both bits of a key sit in ONE 64-bit word of its 64-B line, so the build
+ * sets them with a single 64-bit atomicOr (random atomics are paid per
+ * request, not per byte) and the probe tests them with one 8-B load.
+ * line_mask = (n_lines - 1); lines of 8 u64 words. */
+__device__ static inline uint64_t bloom_bits(uint64_t x) {
+    return (1ull << ((x >> 35) & 63u)) | (1ull << ((x >> 41) & 63u));
+}
+__device__ static inline size_t bloom_word(uint64_t x, uint32_t line_mask) {
+    return (size_t)((uint32_t)x & line_mask) * 8 + ((uint32_t)(x >> 32) & 7u);
 }
 
 __device__ static inline bool bloom_test(const uint32_t *bloom,
                                          uint32_t line_mask, int64_t key) {
     uint64_t x = bloom_mix(key);
-    const uint32_t *line = bloom + ((uint32_t)x & line_mask) * 16;
-    uint32_t b1 = (uint32_t)(x >> 32) & 511u;
-    uint32_t b2 = (uint32_t)(x >> 41) & 511u;
-    if (!(line[b1 >> 5] & (1u << (b1 & 31)))) return false;
-    return (line[b2 >> 5] & (1u << (b2 & 31))) != 0;
+    uint64_t bits = bloom_bits(x);
+    return (((const uint64_t *)bloom)[bloom_word(x, line_mask)] & bits) == bits;
 }
 
-/* ---- inline-bucket build (plain joins) -------------------------------- */
+/* ---- inline-bucket build (plain joins) --------------------------------
+ * ONE pass over the build rows into a zeroed table: a returning atomicAdd
+ * on the bucket's count word (e[0].pad) hands out the row's rank, ranks
+ * 0..3 store key+pos into their inline slot, later ranks append
+ * (row, rank) to a spill list that two small kernels place afterwards.
+ * Per row that is one random atomic (two with the bloom bits), where the
+ * histogram + cursor + two-bloom-word build paid four. The pad words are
+ * only ever touched atomically here, so a slot store can never clobber a
+ * concurrent count. */
 
-/* overflow run length per bucket (entries beyond the 4 inline slots) */
-__global__ void k_ovf_counts(const uint32_t *counts, int64_t n_buckets,
-                             uint32_t *ovf) {
-    for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-         b < n_buckets; b += (int64_t)gridDim.x * blockDim.x)
-        ovf[b] = counts[b] > 4 ? counts[b] - 4 : 0;
+struct JoinSpill {
+    uint32_t row;
+    uint32_t rank;   /* >= 4: position in the bucket's arrival order */
+};
+
+struct JoinInsertParams {
+    DevColView key0;          /* fast path: the I64 key column */
+    const int32_t *hashes;    /* generic path: k_hash_rows output */
+    const uint8_t *keynull;
+    int fast_i64;
+    int64_t n;
+    uint32_t mask;
+    JoinEntry *table;
+    JoinSpill *spill;         /* capacity n: every row may spill */
+    uint32_t *spill_count;
+    unsigned long long *bloom; /* NULL = no bloom */
+    uint32_t bloom_mask;
+};
+
+/* bucket + entry key of build row i (the entry key is the I64 key itself on
+ * the fast path, the row hash otherwise) */
+__device__ static inline uint32_t join_row_bucket(const JoinInsertParams &P,
+                                                  int64_t i, int64_t &key) {
+    int32_t h;
+    if (P.fast_i64) {
+        key = ((const int64_t *)P.key0.values)[i];
+        h = gx_hash_i64(key);
+    } else {
+        h = P.hashes[i];
+        key = (int64_t)h;
+    }
+    return (uint32_t)gx_mix(h) & P.mask;
 }
 
-/* stamp bucket metadata into the slot pads: e[0].pad = count,
- * e[1].pad = overflow start (both land in the line's first 32-B sector).
- * Runs BEFORE the scatter, which writes only key+pos of each slot. */
-__global__ void k_bucket_meta(const uint32_t *counts, const uint32_t *ovf_starts,
-                              int64_t n_buckets, JoinEntry *table) {
-    for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-         b < n_buckets; b += (int64_t)gridDim.x * blockDim.x) {
-        table[b * 4 + 0].pad = counts[b];
-        table[b * 4 + 1].pad = ovf_starts[b];
+__global__ void k_join_insert(JoinInsertParams P) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    /* wave-uniform trip count: the spill append ballots across the wave */
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;;
+         i += stride) {
+        bool live = i < P.n;
+        if (!__ballot(live)) break;
+        /* NULL-key build rows never inserted
+         * (ExecUtils.buildOneChunk:933-941) */
+        if (live)
+            live = P.fast_i64 ? !col_is_null(P.key0, i) : !P.keynull[i];
+        uint32_t rank = 0;
+        if (live) {
+            int64_t key;
+            uint32_t b = join_row_bucket(P, i, key);
+            JoinEntry *bucket = P.table + (uint64_t)b * 4;
+            rank = atomicAdd(&bucket[0].pad, 1u);
+            if (rank < 4) {
+                bucket[rank].key = key;   /* 12-B store; pad untouched */
+                bucket[rank].pos = (uint32_t)i;
+            }
+            if (P.bloom) {
+                uint64_t x = bloom_mix(key);
+                atomicOr(&P.bloom[bloom_word(x, P.bloom_mask)],
+                         (unsigned long long)bloom_bits(x));
+            }
+        }
+        /* wave-aggregated append: one counter atomic per wave (a per-lane
+         * add on one word serializes at ~88/us) */
+        bool spilled = live && rank >= 4;
+        unsigned long long m = __ballot(spilled);
+        if (m) {
+            int leader = __ffsll((long long)m) - 1;
+            uint32_t base = 0;
+            if (lane == leader)
+                base = atomicAdd(P.spill_count, (uint32_t)__popcll(m));
+            base = (uint32_t)__shfl((int)base, leader, 64);
+            if (spilled) {
+                JoinSpill s;
+                s.row = (uint32_t)i;
+                s.rank = rank;
+                P.spill[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = s;
+            }
+        }
     }
 }
 
-__global__ void k_join_scatter_ib(const int32_t *hashes, const uint8_t *keynull,
-                                  int64_t n, uint32_t *cursors,
-                                  const uint32_t *ovf_starts, uint32_t mask,
-                                  JoinEntry *table, JoinEntry *ovf,
-                                  DevColView key0, int fast_i64) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        if (keynull[i]) continue;
-        uint32_t b = (uint32_t)gx_mix(hashes[i]) & mask;
-        uint32_t rank = atomicAdd(&cursors[b], 1u);
-        int64_t key = fast_i64 ? ((const int64_t *)key0.values)[i]
-                               : (int64_t)hashes[i];
-        if (rank < 4) {
-            JoinEntry *t = &table[(uint64_t)b * 4 + rank];
-            t->key = key;       /* pad untouched: carries bucket metadata */
-            t->pos = (uint32_t)i;
-        } else {
-            JoinEntry e;
-            e.key = key;
-            e.pos = (uint32_t)i;
-            e.pad = 0;
-            ovf[ovf_starts[b] + (rank - 4)] = e;
+/* spill pass 1: the rank-4 entry of each overflowing bucket reserves the
+ * bucket's contiguous run (count - 4 entries) and publishes its start in
+ * e[1].pad. Reservations are summed across the wave first, so the cursor
+ * takes one atomic per wave. */
+__global__ void k_join_spill_reserve(JoinInsertParams P, uint32_t n_spill,
+                                     uint32_t *cursor) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;;
+         s += stride) {
+        bool live = s < (int64_t)n_spill;
+        if (!__ballot(live)) break;
+        uint32_t want = 0;
+        JoinEntry *bucket = nullptr;
+        if (live && P.spill[s].rank == 4) {
+            int64_t key;
+            uint32_t b = join_row_bucket(P, P.spill[s].row, key);
+            bucket = P.table + (uint64_t)b * 4;
+            want = bucket[0].pad - 4;
         }
+        /* inclusive wave scan of want */
+        uint32_t incl = want;
+        for (int off = 1; off < 64; off <<= 1) {
+            uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64);
+            if (lane >= off) incl += t;
+        }
+        uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
+        if (total) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(cursor, total);
+            base = (uint32_t)__shfl((int)base, 0, 64);
+            if (want) bucket[1].pad = base + incl - want;
+        }
+    }
+}
+
+/* spill pass 2: every spilled row lands at run start + (rank - 4) */
+__global__ void k_join_spill_place(JoinInsertParams P, uint32_t n_spill,
+                                   JoinEntry *ovf) {
+    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         s < (int64_t)n_spill; s += (int64_t)gridDim.x * blockDim.x) {
+        JoinSpill sp = P.spill[s];
+        int64_t key;
+        uint32_t b = join_row_bucket(P, sp.row, key);
+        JoinEntry e;
+        e.key = key;
+        e.pos = sp.row;
+        e.pad = 0;
+        ovf[P.table[(uint64_t)b * 4 + 1].pad + (sp.rank - 4)] = e;
     }
 }
 
@@ -1172,9 +1262,11 @@ struct JoinOp : gx_op {
     DevBuf d_pn, d_ph, d_meta, d_bpos, d_pidx; /* reused across probe calls */
     DevBuf d_scan_tmp;
     DevBuf d_bitmap;         /* build_outer matched bitmap */
-    DevBuf d_entries, d_starts, d_counts; /* CSR (null_safe) / IB overflow */
-    DevBuf d_keynull, d_hashes;
+    DevBuf d_entries, d_starts; /* CSR (null_safe) / IB overflow runs */
+    DevBuf d_keynull, d_hashes; /* generic keys and CSR builds only */
     DevBuf d_table;          /* inline-bucket table (plain joins) */
+    DevBuf d_spill;          /* IB build: rows whose bucket was full */
+    DevBuf d_counts;         /* CSR cursors / IB spill count + run cursor */
     DevStore probe_buf;      /* buffered-probe staging (probe_push/flush) */
     bool probe_buf_init = false;
     DevStore build;          /* build-side columns in HBM */
@@ -1309,110 +1401,114 @@ struct JoinOp : gx_op {
                                       stream));
             }
         }
-        if (n > 0) {
+        if (n > 0 && null_safe_keys) {
             if (d_hashes.grow((size_t)n * 4, stream) ||
                 d_keynull.grow((size_t)n, stream)) return -1;
             KeyViews bk = key_views(build, build_key_cols);
             hipLaunchKernelGGL(k_hash_rows, dim3(gx_grid(n)), dim3(256), 0, stream,
                                bk, n, (int32_t *)d_hashes.p, (uint8_t *)d_keynull.p,
-                               (int)null_safe_keys);
-            if (null_safe_keys) {
-                /* CSR layout for the group-join kernels (linear entry
-                 * enumeration); plain joins use the inline-bucket table. */
-                n_buckets = gx_pow2(n * 2); /* avg load 0.5 */
-                mask = (uint32_t)(n_buckets - 1);
-                if (d_counts.grow((size_t)(n_buckets + 1) * 4, stream) ||
-                    d_starts.grow((size_t)(n_buckets + 1) * 4, stream) ||
-                    d_entries.grow((size_t)n * sizeof(JoinEntry), stream)) return -1;
-                HIP_OK(hipMemsetAsync(d_counts.p, 0, (size_t)(n_buckets + 1) * 4, stream));
-                hipLaunchKernelGGL(k_join_hist, dim3(gx_grid(n)), dim3(256), 0, stream,
-                                   (const int32_t *)d_hashes.p, (const uint8_t *)d_keynull.p,
-                                   n, (uint32_t *)d_counts.p, mask);
-                /* exclusive scan counts[0..n_buckets] -> starts (incl. total) */
-                if (cub_run(d_scan_tmp, stream, [&](void *t, size_t &b) {
-                        return hipcub::DeviceScan::ExclusiveSum(
-                            t, b, (uint32_t *)d_counts.p, (uint32_t *)d_starts.p,
-                            n_buckets + 1, stream);
-                    }))
-                    return -1;
-                /* reuse counts as cursors (= starts) */
-                HIP_OK(hipMemcpyAsync(d_counts.p, d_starts.p, (size_t)n_buckets * 4,
-                                      hipMemcpyDeviceToDevice, stream));
-                hipLaunchKernelGGL(k_join_scatter, dim3(gx_grid(n)), dim3(256), 0, stream,
-                                   (const int32_t *)d_hashes.p, (const uint8_t *)d_keynull.p,
-                                   n, (uint32_t *)d_counts.p, mask,
-                                   (JoinEntry *)d_entries.p,
-                                   build.view(build_key_cols[0]), (int)fast_i64);
-            } else {
-                /* inline-bucket build: hist -> overflow-run scan -> bucket
-                 * metadata stamp -> scatter (key+pos only; pads carry the
-                 * metadata). Load cap 0.75: at load ~0.9 the lazy e1..e3
-                 * slot loads frequently miss L2 (the wave's other random
-                 * fetches churn ~a full XCD L2 per iteration) and C2's
-                 * probe paid ~1.7 HBM lines/row (r2 PMC: 7.3 GB for a
-                 * 60M-row probe) — one extra doubling buys ~1 line/row. */
-                n_buckets = gx_pow2(n); /* 4 slots/bucket */
-                if (n > (n_buckets * 3) / 4) n_buckets <<= 1;
-                mask = (uint32_t)(n_buckets - 1);
-                if (d_counts.grow((size_t)(n_buckets + 1) * 4, stream) ||
-                    d_starts.grow((size_t)(n_buckets + 1) * 4, stream) ||
-                    d_table.grow((size_t)n_buckets * 4 * sizeof(JoinEntry),
-                                 stream)) return -1;
-                HIP_OK(hipMemsetAsync(d_counts.p, 0, (size_t)(n_buckets + 1) * 4, stream));
-                hipLaunchKernelGGL(k_join_hist, dim3(gx_grid(n)), dim3(256), 0, stream,
-                                   (const int32_t *)d_hashes.p, (const uint8_t *)d_keynull.p,
-                                   n, (uint32_t *)d_counts.p, mask);
-                hipLaunchKernelGGL(k_ovf_counts, dim3(gx_grid(n_buckets)), dim3(256),
-                                   0, stream, (const uint32_t *)d_counts.p,
-                                   n_buckets, (uint32_t *)d_starts.p);
-                if (cub_run(d_scan_tmp, stream, [&](void *t, size_t &b) {
-                        return hipcub::DeviceScan::ExclusiveSum(
-                            t, b, (uint32_t *)d_starts.p, (uint32_t *)d_starts.p,
-                            n_buckets + 1, stream);
-                    }))
-                    return -1;
-                uint32_t total_ovf = 0;
-                HIP_OK(hipMemcpyAsync(&total_ovf,
-                                      (uint32_t *)d_starts.p + n_buckets, 4,
-                                      hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipStreamSynchronize(stream));
-                if (d_entries.grow((size_t)std::max<uint32_t>(total_ovf, 1) *
-                                       sizeof(JoinEntry), stream)) return -1;
-                hipLaunchKernelGGL(k_bucket_meta, dim3(gx_grid(n_buckets)),
-                                   dim3(256), 0, stream,
-                                   (const uint32_t *)d_counts.p,
-                                   (const uint32_t *)d_starts.p, n_buckets,
-                                   (JoinEntry *)d_table.p);
-                HIP_OK(hipMemsetAsync(d_counts.p, 0, (size_t)n_buckets * 4, stream));
-                hipLaunchKernelGGL(k_join_scatter_ib, dim3(gx_grid(n)), dim3(256),
-                                   0, stream,
-                                   (const int32_t *)d_hashes.p,
-                                   (const uint8_t *)d_keynull.p,
-                                   n, (uint32_t *)d_counts.p,
-                                   (const uint32_t *)d_starts.p, mask,
-                                   (JoinEntry *)d_table.p,
-                                   (JoinEntry *)d_entries.p,
-                                   build.view(build_key_cols[0]), (int)fast_i64);
-                /* bloom pre-filter: GX_BLOOM=1 forces on, =0 off; default
-                 * on for builds whose table exceeds the Infinity Cache
-                 * while the bloom (8 bits/key) still fits (the regime
-                 * where a negative saves a random HBM line) */
-                const char *be = getenv("GX_BLOOM");
-                bool use_bloom = fast_i64 &&
-                    (be ? be[0] == '1'
-                        : (cfg.enable_bloom == 1 && n >= (1 << 16) &&
-                           n <= INT64_C(200) << 20));
-                if (use_bloom) {
-                    int64_t n_lines = gx_pow2(std::max<int64_t>(n / 64, 1));
-                    bloom_mask = (uint32_t)(n_lines - 1);
-                    if (d_bloom.grow((size_t)n_lines * 64, stream)) return -1;
-                    HIP_OK(hipMemsetAsync(d_bloom.p, 0, (size_t)n_lines * 64,
-                                          stream));
-                    hipLaunchKernelGGL(k_bloom_set, dim3(gx_grid(n)),
-                                       dim3(256), 0, stream,
-                                       build.view(build_key_cols[0]), n,
-                                       (uint32_t *)d_bloom.p, bloom_mask);
-                }
+                               1);
+            /* CSR layout for the group-join kernels (linear entry
+             * enumeration); plain joins use the inline-bucket table. */
+            n_buckets = gx_pow2(n * 2); /* avg load 0.5 */
+            mask = (uint32_t)(n_buckets - 1);
+            if (d_counts.grow((size_t)(n_buckets + 1) * 4, stream) ||
+                d_starts.grow((size_t)(n_buckets + 1) * 4, stream) ||
+                d_entries.grow((size_t)n * sizeof(JoinEntry), stream)) return -1;
+            HIP_OK(hipMemsetAsync(d_counts.p, 0, (size_t)(n_buckets + 1) * 4, stream));
+            hipLaunchKernelGGL(k_join_hist, dim3(gx_grid(n)), dim3(256), 0, stream,
+                               (const int32_t *)d_hashes.p, (const uint8_t *)d_keynull.p,
+                               n, (uint32_t *)d_counts.p, mask);
+            /* exclusive scan counts[0..n_buckets] -> starts (incl. total) */
+            if (cub_run(d_scan_tmp, stream, [&](void *t, size_t &b) {
+                    return hipcub::DeviceScan::ExclusiveSum(
+                        t, b, (uint32_t *)d_counts.p, (uint32_t *)d_starts.p,
+                        n_buckets + 1, stream);
+                }))
+                return -1;
+            /* reuse counts as cursors (= starts) */
+            HIP_OK(hipMemcpyAsync(d_counts.p, d_starts.p, (size_t)n_buckets * 4,
+                                  hipMemcpyDeviceToDevice, stream));
+            hipLaunchKernelGGL(k_join_scatter, dim3(gx_grid(n)), dim3(256), 0, stream,
+                               (const int32_t *)d_hashes.p, (const uint8_t *)d_keynull.p,
+                               n, (uint32_t *)d_counts.p, mask,
+                               (JoinEntry *)d_entries.p,
+                               build.view(build_key_cols[0]), (int)fast_i64);
+        } else if (n > 0) {
+            /* inline-bucket build, one pass (see k_join_insert): zero the
+             * table with a streaming memset, insert, then place the few
+             * rows that found their bucket full. Load cap 0.75: at load
+             * ~0.9 the lazy e1..e3 slot loads frequently miss L2 (the
+             * wave's other random fetches churn ~a full XCD L2 per
+             * iteration) and C2's probe paid ~1.7 HBM lines/row (r2 PMC:
+             * 7.3 GB for a 60M-row probe) — one extra doubling buys
+             * ~1 line/row. */
+            if (n >= INT64_C(0xFFFFFFFF)) {
+                gx_set_err("join build: more than 2^32-2 rows");
+                return -1;
+            }
+            n_buckets = gx_pow2(n); /* 4 slots/bucket */
+            if (n > (n_buckets * 3) / 4) n_buckets <<= 1;
+            mask = (uint32_t)(n_buckets - 1);
+            const size_t table_bytes = (size_t)n_buckets * 4 * sizeof(JoinEntry);
+            /* spill list sized for the worst case (every row one key) */
+            if (d_counts.grow(8, stream) ||
+                d_spill.grow((size_t)n * sizeof(JoinSpill), stream) ||
+                d_table.grow(table_bytes, stream)) return -1;
+            HIP_OK(hipMemsetAsync(d_table.p, 0, table_bytes, stream));
+            HIP_OK(hipMemsetAsync(d_counts.p, 0, 8, stream));
+            if (!fast_i64) {
+                /* generic keys: the row hash is the entry key */
+                if (d_hashes.grow((size_t)n * 4, stream) ||
+                    d_keynull.grow((size_t)n, stream)) return -1;
+                hipLaunchKernelGGL(k_hash_rows, dim3(gx_grid(n)), dim3(256), 0,
+                                   stream, key_views(build, build_key_cols), n,
+                                   (int32_t *)d_hashes.p, (uint8_t *)d_keynull.p,
+                                   0);
+            }
+            /* bloom pre-filter: GX_BLOOM=1 forces on, =0 off; default
+             * on for builds whose table exceeds the Infinity Cache
+             * while the bloom (8 bits/key) still fits (the regime
+             * where a negative saves a random HBM line) */
+            const char *be = getenv("GX_BLOOM");
+            bool use_bloom = fast_i64 &&
+                (be ? be[0] == '1'
+                    : (cfg.enable_bloom == 1 && n >= (1 << 16) &&
+                       n <= INT64_C(200) << 20));
+            if (use_bloom) {
+                int64_t n_lines = gx_pow2(std::max<int64_t>(n / 64, 1));
+                bloom_mask = (uint32_t)(n_lines - 1);
+                if (d_bloom.grow((size_t)n_lines * 64, stream)) return -1;
+                HIP_OK(hipMemsetAsync(d_bloom.p, 0, (size_t)n_lines * 64,
+                                      stream));
+            }
+            JoinInsertParams IP;
+            IP.key0 = build.view(build_key_cols[0]);
+            IP.hashes = (const int32_t *)d_hashes.p;
+            IP.keynull = (const uint8_t *)d_keynull.p;
+            IP.fast_i64 = (int)fast_i64;
+            IP.n = n;
+            IP.mask = mask;
+            IP.table = (JoinEntry *)d_table.p;
+            IP.spill = (JoinSpill *)d_spill.p;
+            IP.spill_count = (uint32_t *)d_counts.p;
+            IP.bloom = use_bloom ? (unsigned long long *)d_bloom.p : nullptr;
+            IP.bloom_mask = bloom_mask;
+            hipLaunchKernelGGL(k_join_insert, dim3(gx_grid(n)), dim3(256), 0,
+                               stream, IP);
+            uint32_t n_spill = 0;
+            HIP_OK(hipMemcpyAsync(&n_spill, d_counts.p, 4,
+                                  hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            if (d_entries.grow((size_t)std::max<uint32_t>(n_spill, 1) *
+                                   sizeof(JoinEntry), stream)) return -1;
+            if (n_spill > 0) {
+                hipLaunchKernelGGL(k_join_spill_reserve, dim3(gx_grid(n_spill)),
+                                   dim3(256), 0, stream, IP, n_spill,
+                                   (uint32_t *)d_counts.p + 1);
+                hipLaunchKernelGGL(k_join_spill_place, dim3(gx_grid(n_spill)),
+                                   dim3(256), 0, stream, IP, n_spill,
+                                   (JoinEntry *)d_entries.p);
             }
         }
 
@@ -1438,6 +1534,7 @@ struct JoinOp : gx_op {
             HIP_OK(hipMemsetAsync(d_bitmap.p, 0, words * 4, stream));
         }
         HIP_OK(hipStreamSynchronize(stream));
+        d_spill.reset(); /* build-time scratch only */
         built = true;
         return 0;
     }

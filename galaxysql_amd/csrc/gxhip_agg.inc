@@ -89,7 +89,10 @@ __device__ static inline bool packed_equal(const PackedKey *packed,
                                            const uint8_t *nullmask,
                                            int64_t a, int64_t b) {
     PackedKey pa = packed[a], pb = packed[b];
-    return pa.lo == pb.lo && pa.hi == pb.hi && nullmask[a] == nullmask[b];
+    if (pa.lo != pb.lo || pa.hi != pb.hi) return false;
+    /* nullmask == NULL: no key column has carried a NULL so far, every
+     * mask byte is 0 — skip the second random request */
+    return !nullmask || nullmask[a] == nullmask[b];
 }
 
 /* Java Math.min/max semantics for doubles (NaN propagates, -0.0 < +0.0) */
@@ -508,28 +511,70 @@ __global__ void k_agg_accumulate(AggAccumParams P) {
     }
 }
 
-/* emit agg value columns: record field -> values + nulls */
-__global__ void k_agg_emit(const unsigned long long *records, int32_t stride,
-                           int32_t val_off, int32_t seen_off,
-                           int32_t func, uint32_t n_groups,
-                           const uint32_t *slot_of_gid,
-                           void *out_vals, uint8_t *out_nulls) {
-    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < n_groups;
+/* Emission, one kernel for the whole result: each group's record (a random
+ * line in slot mode) is read ONCE and every aggregate's value + null flag
+ * written from it; with packed null-free keys the group-key columns come
+ * out of the group's 16-B packed record as well (one random read per group
+ * instead of one gather per key column). */
+struct AggEmitParams {
+    const unsigned long long *records;
+    int32_t stride;
+    uint32_t n_groups;
+    const uint32_t *slot_of_gid;   /* slot mode; NULL = records[gid] */
+    int32_t n_aggs;
+    int32_t func[GX_MAX_COLS];
+    int32_t val_off[GX_MAX_COLS];
+    int32_t seen_off[GX_MAX_COLS];
+    void *out_vals[GX_MAX_COLS];
+    uint8_t *out_nulls[GX_MAX_COLS];
+    int32_t n_keys;                /* 0 = key columns gathered separately */
+    int32_t key_type[GX_MAX_KEYS];
+    const PackedKey *packed;
+    const uint32_t *krow_of_gid;
+    void *key_vals[GX_MAX_KEYS];
+    uint8_t *key_nulls[GX_MAX_KEYS];
+};
+
+__global__ void k_agg_emit(AggEmitParams P) {
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < P.n_groups;
          g += gridDim.x * blockDim.x) {
-        const size_t rec_idx = slot_of_gid ? slot_of_gid[g] : g;
-        const unsigned long long *rec = records + rec_idx * stride;
-        bool isnull = seen_off >= 0 && rec[seen_off] == 0ull;
-        out_nulls[g] = isnull;
-        bool f64 = func == GX_AGG_SUM_F64 || func == GX_AGG_MIN_F64 ||
-                   func == GX_AGG_MAX_F64 || func == GX_AGG_AVG_F64;
-        unsigned long long v = isnull ? 0ull : rec[val_off];
-        if (func == GX_AGG_AVG_F64)
-            ((double *)out_vals)[g] = isnull ? 0.0
-                : __builtin_bit_cast(double, v) / (double)rec[seen_off];
-        else if (f64)
-            ((double *)out_vals)[g] = isnull ? 0.0 : __builtin_bit_cast(double, v);
-        else
-            ((int64_t *)out_vals)[g] = (int64_t)v;
+        if (P.n_keys > 0) {
+            const PackedKey pk = P.packed[P.krow_of_gid[g]];
+            const uint8_t *bytes = (const uint8_t *)&pk;
+            int off = 0;
+            for (int c = 0; c < P.n_keys; c++) {
+                P.key_nulls[c][g] = 0;
+                if (P.key_type[c] == GX_I32) {
+                    uint32_t v;
+                    __builtin_memcpy(&v, bytes + off, 4);
+                    ((uint32_t *)P.key_vals[c])[g] = v;
+                    off += 4;
+                } else {
+                    uint64_t v;
+                    __builtin_memcpy(&v, bytes + off, 8);
+                    ((uint64_t *)P.key_vals[c])[g] = v;
+                    off += 8;
+                }
+            }
+        }
+        const size_t rec_idx = P.slot_of_gid ? P.slot_of_gid[g] : g;
+        const unsigned long long *rec = P.records + rec_idx * P.stride;
+        for (int a = 0; a < P.n_aggs; a++) {
+            const int32_t func = P.func[a], seen_off = P.seen_off[a];
+            bool isnull = seen_off >= 0 && rec[seen_off] == 0ull;
+            P.out_nulls[a][g] = isnull;
+            bool f64 = func == GX_AGG_SUM_F64 || func == GX_AGG_MIN_F64 ||
+                       func == GX_AGG_MAX_F64 || func == GX_AGG_AVG_F64;
+            unsigned long long v = isnull ? 0ull : rec[P.val_off[a]];
+            if (func == GX_AGG_AVG_F64)
+                ((double *)P.out_vals[a])[g] = isnull ? 0.0
+                    : __builtin_bit_cast(double, v) / (double)rec[seen_off];
+            else if (f64)
+                ((double *)P.out_vals[a])[g] =
+                    isnull ? 0.0 : __builtin_bit_cast(double, v);
+            else
+                ((int64_t *)P.out_vals[a])[g] = (int64_t)v;
+        }
     }
 }
 
@@ -742,7 +787,8 @@ struct AggOp : gx_op {
     DevBuf d_slotidx, d_total, d_tiles, d_hashes, d_krow_of_gid, d_slots;
     DevBuf d_nullmask, d_packed;  /* packed fast-path key records */
     DevStore keystore;         /* appended group-key columns (for emit) */
-    bool slot_records = false; /* records indexed by slot (stride <= 2) */
+    bool slot_records = false; /* records indexed by slot (narrow state) */
+    bool tmpl_zero = true;     /* identity record is all zero bits */
     int32_t stride = 0;        /* record size in u64s */
     int32_t val_off[GX_MAX_COLS] = {0};
     int32_t seen_off[GX_MAX_COLS] = {0};
@@ -829,10 +875,19 @@ struct AggOp : gx_op {
             }
         }
         stride = off > 0 ? off : 1;
+        for (int32_t k = 0; k < stride; k++)
+            if (tmpl[k] != 0ull) tmpl_zero = false;
         /* slot-indexed state: the accumulate RMW lands on records[slot]
-         * directly (one random line/row). Memory = n_slots x stride x 8
-         * (2x the group count at load 0.5), so gate on narrow state. */
-        slot_records = stride <= 2 && cfg.n_group_cols > 0;
+         * directly (one random line/row) and fuses into the insert pass.
+         * Memory = n_slots x stride x 8 (2x the group count at load 0.5),
+         * so gate on narrow state: records of up to GX_AGG_SLOT_STRIDE
+         * u64s (default 4, clamped to 1..4; 2 = the pre-round-4 gate). */
+        int32_t slot_stride_max = 4;
+        if (const char *se = getenv("GX_AGG_SLOT_STRIDE")) {
+            int v = atoi(se);
+            if (v >= 1 && v <= 4) slot_stride_max = v;
+        }
+        slot_records = stride <= slot_stride_max && cfg.n_group_cols > 0;
         /* a distinct agg accumulates by gid from its own pass: state is
          * gid-indexed (gids never move) */
         if (has_distinct) slot_records = false;
@@ -844,10 +899,16 @@ struct AggOp : gx_op {
 
     int64_t max_fill() const { return n_slots / 2; }
 
-    int init_state_range(int64_t from, int64_t to) {
+    /* identity-initialize records [from, to) of buf */
+    int init_records(void *buf, int64_t from, int64_t to) {
         if (to <= from) return 0;
+        if (tmpl_zero) {
+            HIP_OK(hipMemsetAsync((char *)buf + (size_t)from * stride * 8, 0,
+                                  (size_t)(to - from) * stride * 8, stream));
+            return 0;
+        }
         AggInitParams P;
-        P.records = (unsigned long long *)d_records.p;
+        P.records = (unsigned long long *)buf;
         P.stride = stride;
         P.from = from;
         P.to = to;
@@ -855,6 +916,9 @@ struct AggOp : gx_op {
         hipLaunchKernelGGL(k_agg_init, dim3(gx_grid((to - from) * stride)),
                            dim3(256), 0, stream, P);
         return 0;
+    }
+    int init_state_range(int64_t from, int64_t to) {
+        return init_records(d_records.p, from, to);
     }
 
     int ensure_group_cap(int64_t need) {
@@ -886,6 +950,15 @@ struct AggOp : gx_op {
         }
     }
 
+    /* any group-key column has carried a NULL so far (sticky per column;
+     * checked after the chunk's keys are appended, so it covers both sides
+     * of every compare) */
+    bool keys_have_nulls() const {
+        for (const auto &c : keystore.cols)
+            if (c.has_nulls) return true;
+        return false;
+    }
+
     KeyViews keystore_views() const {
         KeyViews kv;
         kv.n = (int32_t)keystore.cols.size();
@@ -905,14 +978,7 @@ struct AggOp : gx_op {
         HIP_OK(hipMemsetAsync(new_slots.p, 0, (size_t)ns * sizeof(AggSlot), stream));
         if (slot_records) {
             if (new_records.grow((size_t)ns * stride * 8, stream)) return -1;
-            AggInitParams P;
-            P.records = (unsigned long long *)new_records.p;
-            P.stride = stride;
-            P.from = 0;
-            P.to = ns;
-            std::memcpy(P.tmpl, tmpl, sizeof(tmpl));
-            hipLaunchKernelGGL(k_agg_init, dim3(gx_grid(ns * stride)),
-                               dim3(256), 0, stream, P);
+            if (init_records(new_records.p, 0, ns)) return -1;
         }
         if (n_slots > 0 && d_slots.p) {
             /* migrate occupied slots (incl. pending ones) + their state */
@@ -1117,7 +1183,8 @@ struct AggOp : gx_op {
                 IP.mask = mask;
                 IP.use_packed = (int)use_packed;
                 IP.packed = (const PackedKey *)d_packed.p;
-                IP.nullmask = (const uint8_t *)d_nullmask.p;
+                IP.nullmask = keys_have_nulls()
+                                  ? (const uint8_t *)d_nullmask.p : nullptr;
                 IP.keystore = keystore_views();
                 IP.hashes = (const int32_t *)d_hashes.p;
                 IP.base_krow = base_krow;
@@ -1199,7 +1266,8 @@ struct AggOp : gx_op {
             AP.mask = mask;
             AP.use_packed = (int)use_packed;
             AP.packed = (const PackedKey *)d_packed.p;
-            AP.nullmask = (const uint8_t *)d_nullmask.p;
+            AP.nullmask = keys_have_nulls()
+                              ? (const uint8_t *)d_nullmask.p : nullptr;
             AP.keystore = keystore_views();
             AP.hashes = (const int32_t *)d_hashes.p;
             AP.base_krow = base_krow;
@@ -1261,8 +1329,24 @@ struct AggOp : gx_op {
         auto h = alloc_result_cols(otypes, ng, device, stream);
         if (!h) return -1;
         if (ng > 0) {
+            AggEmitParams EP;
+            std::memset(&EP, 0, sizeof(EP));
             size_t col = 0;
+            /* packed null-free keys ride along in k_agg_emit */
+            const bool packed_keys = use_packed && !keys_have_nulls();
+            if (packed_keys) {
+                EP.n_keys = (int32_t)group_cols_.size();
+                EP.packed = (const PackedKey *)d_packed.p;
+                EP.krow_of_gid = (const uint32_t *)d_krow_of_gid.p;
+            }
             for (size_t kc = 0; kc < group_cols_.size(); kc++) {
+                if (packed_keys) {
+                    EP.key_type[kc] = otypes[kc];
+                    EP.key_vals[kc] = h->bufs[col * 2].p;
+                    EP.key_nulls[kc] = (uint8_t *)h->bufs[col * 2 + 1].p;
+                    col++;
+                    continue;
+                }
                 DevColView kv = keystore.view((int32_t)kc);
                 if (kv.type == GX_SLICE) {
                     if (gather_slice_col(kv, (const uint32_t *)d_krow_of_gid.p,
@@ -1278,18 +1362,23 @@ struct AggOp : gx_op {
                                    h->bufs[col * 2].p, (uint8_t *)h->bufs[col * 2 + 1].p, 0);
                 col++;
             }
+            EP.records = (const unsigned long long *)d_records.p;
+            EP.stride = stride;
+            EP.n_groups = ng;
+            EP.slot_of_gid = slot_records ? (const uint32_t *)d_slot_of_gid.p
+                                          : nullptr;
+            EP.n_aggs = (int32_t)aggs.size();
             for (size_t a = 0; a < aggs.size(); a++) {
-                hipLaunchKernelGGL(k_agg_emit, dim3(gx_grid(ng)), dim3(256), 0, stream,
-                                   (const unsigned long long *)d_records.p,
-                                   stride, val_off[a], seen_off[a],
-                                   aggs[a].func, ng,
-                                   slot_records
-                                       ? (const uint32_t *)d_slot_of_gid.p
-                                       : nullptr,
-                                   h->bufs[col * 2].p,
-                                   (uint8_t *)h->bufs[col * 2 + 1].p);
+                EP.func[a] = aggs[a].func;
+                EP.val_off[a] = val_off[a];
+                EP.seen_off[a] = seen_off[a];
+                EP.out_vals[a] = h->bufs[col * 2].p;
+                EP.out_nulls[a] = (uint8_t *)h->bufs[col * 2 + 1].p;
                 col++;
             }
+            if (EP.n_aggs > 0 || EP.n_keys > 0)
+                hipLaunchKernelGGL(k_agg_emit, dim3(gx_grid(ng)), dim3(256), 0,
+                                   stream, EP);
             HIP_OK(hipStreamSynchronize(stream));
         }
         give_result(std::move(h), out);
