@@ -684,12 +684,16 @@ __device__ static inline void emit_flush(const ProbeParams &P, EmitStage &E) {
     E.cnt = 0;
 }
 
+/* STAGE = slots in this wave's LDS slice (>= 64: one call adds up to a
+ * full wave of pairs). k_probe stages GX_EMIT_STAGE; the fused probe-scan
+ * kernel, whose matches are sparse, a smaller one (gxhip_scan.inc). */
+template <uint32_t STAGE = GX_EMIT_STAGE>
 __device__ static inline void emit_pair(const ProbeParams &P, EmitStage &E,
                                         bool want, uint32_t pidx, uint32_t bpos) {
     unsigned long long m = __ballot(want);
     if (!m) return;
     uint32_t n = (uint32_t)__popcll(m);
-    if (E.cnt + n > GX_EMIT_STAGE) emit_flush(P, E);
+    if (E.cnt + n > STAGE) emit_flush(P, E);
     if (want) {
         uint32_t at = E.cnt + (uint32_t)__popcll(m & ((1ull << E.lane) - 1ull));
         E.s_p[at] = pidx;
@@ -698,61 +702,21 @@ __device__ static inline void emit_pair(const ProbeParams &P, EmitStage &E,
     E.cnt += n;
 }
 
-/* Process one probe row (or staged row at index bi), wave-synchronously:
- * the whole wave calls this together so ballot-compaction in emit_pair
- * sees every lane. One random 64-B line resolves the whole bucket: e0
- * carries the entry count in its pad; e1 (lazily loaded, same line)
- * carries the overflow start. In the fast path the bucket hash is
- * computed inline from the key column — no k_hash_rows pass, no
- * hashes/keynull loads.
- *
- * (Negative result, r2 A/B: per-thread 4-row batching of the e0 load
- * chains — extra MLP — ran join2 at 13.8 ms vs 11.0 ms unbatched even
- * with the slot arrays in registers; the ~8 resident waves/SIMD already
- * overlap the walk. The lever that pays is bucket-clustered staging.) */
-__device__ static inline void probe_one(const ProbeParams &P, EmitStage &E,
-                                        bool active, int64_t bi) {
-    uint32_t i = 0;
+/* The candidate walk for one probe row per lane, wave-synchronously: the
+ * whole wave calls this together so ballot-compaction in emit_pair sees
+ * every lane. The caller has resolved the lane's bucket: e0 is its first
+ * slot (already loaded; its pad carries the entry count `end`, 0 when the
+ * lane has nothing to walk), ebase its slot index; e1 (lazily loaded, same
+ * 64-B line) carries the overflow start. Shared by probe_one (k_probe)
+ * and probe_key (the fused probe-scan kernel). */
+template <uint32_t STAGE = GX_EMIT_STAGE>
+__device__ static inline void probe_walk(const ProbeParams &P, EmitStage &E,
+                                         bool active, uint32_t i,
+                                         int64_t want_key, JoinEntry e0,
+                                         uint64_t ebase, uint32_t end) {
     bool matched = false;
-    uint32_t it = 0, end = 0;
-    int64_t want_key = 0;
-    JoinEntry e0 = {0, 0, 0};
-    uint64_t ebase = 0;
+    uint32_t it = 0;
     uint32_t ovf0 = 0;
-    if (P.staged) {
-        RadixRow r = active ? P.staged[bi] : RadixRow{0x80000000u, 0, 0};
-        i = r.rowid & 0x7FFFFFFFu;
-        if (active && !(r.rowid & 0x80000000u)) {
-            want_key = r.key;
-            if (!P.bloom || bloom_test(P.bloom, P.bloom_mask, want_key)) {
-                uint32_t b = (uint32_t)gx_mix(r.hash) & P.mask;
-                ebase = (uint64_t)b * 4;
-                e0 = P.table[ebase];
-                end = e0.pad;
-            }
-        }
-    } else if (P.fast_i64) {
-        i = active ? (uint32_t)bi : 0;
-        const DevColView &kc = P.probe_keys.col[0];
-        if (active && !col_is_null(kc, i)) {
-            want_key = ((const int64_t *)kc.values)[i];
-            if (!P.bloom || bloom_test(P.bloom, P.bloom_mask, want_key)) {
-                uint32_t b = (uint32_t)gx_mix(gx_hash_i64(want_key)) & P.mask;
-                ebase = (uint64_t)b * 4;
-                e0 = P.table[ebase];
-                end = e0.pad;
-            }
-        }
-    } else {
-        i = active ? (uint32_t)bi : 0;
-        if (active && !P.keynull[i]) {
-            uint32_t b = (uint32_t)gx_mix(P.hashes[i]) & P.mask;
-            ebase = (uint64_t)b * 4;
-            e0 = P.table[ebase];
-            end = e0.pad;
-        }
-    }
-
     /* walk candidates; lanes iterate together so emissions batch */
     while (__ballot(it < end)) {
         bool have = active && it < end;
@@ -789,12 +753,12 @@ __device__ static inline void probe_one(const ProbeParams &P, EmitStage &E,
             matched = true;
         }
         bool emit_now = is_match && !P.semi_join;
-        emit_pair(P, E, emit_now, i, bpos);
+        emit_pair<STAGE>(P, E, emit_now, i, bpos);
     }
 
     /* post-row emissions (LEFT/RIGHT null rows, SEMI/ANTI rows) */
     bool want_null_row = active && P.outer_join && !P.build_outer && !matched;
-    emit_pair(P, E, want_null_row, i, 0xFFFFFFFFu);
+    emit_pair<STAGE>(P, E, want_null_row, i, 0xFFFFFFFFu);
     if (P.semi_join) {
         bool want;
         if (P.join_type == GX_JOIN_SEMI) want = active && matched;
@@ -803,8 +767,82 @@ __device__ static inline void probe_one(const ProbeParams &P, EmitStage &E,
             if (want && P.anti_null_col >= 0)
                 want = !col_is_null(P.anti_col, i);
         }
-        emit_pair(P, E, want, i, 0xFFFFFFFFu);
+        emit_pair<STAGE>(P, E, want, i, 0xFFFFFFFFu);
     }
+}
+
+/* Process one probe row (or staged row at index bi), wave-synchronously:
+ * the whole wave calls this together so ballot-compaction in emit_pair
+ * sees every lane. One random 64-B line resolves the whole bucket: e0
+ * carries the entry count in its pad; e1 (lazily loaded, same line)
+ * carries the overflow start. In the fast path the bucket hash is
+ * computed inline from the key column — no k_hash_rows pass, no
+ * hashes/keynull loads.
+ *
+ * (Negative result, r2 A/B, about k_probe only: batching the walk's e0
+ * loads 4 rows per thread ran join2 at 13.8 ms vs 11.0 ms. In k_probe
+ * every lane probes and every probe hits, so the resident waves already
+ * overlap the walk. It says nothing about the fused kernel's streaming
+ * stage, where most lanes have no bucket to fetch: gxhip_scan.inc.) */
+__device__ static inline void probe_one(const ProbeParams &P, EmitStage &E,
+                                        bool active, int64_t bi) {
+    uint32_t i = 0;
+    uint32_t end = 0;
+    int64_t want_key = 0;
+    JoinEntry e0 = {0, 0, 0};
+    uint64_t ebase = 0;
+    if (P.staged) {
+        RadixRow r = active ? P.staged[bi] : RadixRow{0x80000000u, 0, 0};
+        i = r.rowid & 0x7FFFFFFFu;
+        if (active && !(r.rowid & 0x80000000u)) {
+            want_key = r.key;
+            if (!P.bloom || bloom_test(P.bloom, P.bloom_mask, want_key)) {
+                uint32_t b = (uint32_t)gx_mix(r.hash) & P.mask;
+                ebase = (uint64_t)b * 4;
+                e0 = P.table[ebase];
+                end = e0.pad;
+            }
+        }
+    } else if (P.fast_i64) {
+        i = active ? (uint32_t)bi : 0;
+        const DevColView &kc = P.probe_keys.col[0];
+        if (active && !col_is_null(kc, i)) {
+            want_key = ((const int64_t *)kc.values)[i];
+            if (!P.bloom || bloom_test(P.bloom, P.bloom_mask, want_key)) {
+                uint32_t b = (uint32_t)gx_mix(gx_hash_i64(want_key)) & P.mask;
+                ebase = (uint64_t)b * 4;
+                e0 = P.table[ebase];
+                end = e0.pad;
+            }
+        }
+    } else {
+        i = active ? (uint32_t)bi : 0;
+        if (active && !P.keynull[i]) {
+            uint32_t b = (uint32_t)gx_mix(P.hashes[i]) & P.mask;
+            ebase = (uint64_t)b * 4;
+            e0 = P.table[ebase];
+            end = e0.pad;
+        }
+    }
+    probe_walk(P, E, active, i, want_key, e0, ebase, end);
+}
+
+/* Fast-path (fast_i64) probe of an already-resolved (row id, key): the
+ * caller has done the NULL-key and bloom tests. One lane per key, the
+ * whole wave together, like probe_one. */
+template <uint32_t STAGE>
+__device__ static inline void probe_key(const ProbeParams &P, EmitStage &E,
+                                        bool active, uint32_t i, int64_t key) {
+    uint32_t end = 0;
+    JoinEntry e0 = {0, 0, 0};
+    uint64_t ebase = 0;
+    if (active) {
+        uint32_t b = (uint32_t)gx_mix(gx_hash_i64(key)) & P.mask;
+        ebase = (uint64_t)b * 4;
+        e0 = P.table[ebase];
+        end = e0.pad;
+    }
+    probe_walk<STAGE>(P, E, active, i, key, e0, ebase, end);
 }
 
 __global__ void k_probe(ProbeParams P) {

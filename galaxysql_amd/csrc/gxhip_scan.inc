@@ -235,36 +235,210 @@ __device__ static inline void proj_store(int32_t op, int32_t scale,
     }
 }
 
-/* Fused scan + probe (gxop_join_probe_scan fast path): k_probe with a
- * predicate stage in front. Grid-strides over the RAW rows; a lane whose
- * row fails the scan predicates is inactive for probe_one (its NULL-key
- * test, bloom test, bucket walk and emit staging are unchanged and stay
- * wave-synchronous), so the emitted probe index is the raw row id and no
- * projected column is materialized for rows the join drops. Survivors of
- * the predicates are counted per wave in a register (one ballot/popcount
- * per iteration) and added to *kept once per wave. */
-__global__ void k_probe_scan(ProbeParams P, ScanPreds S, uint32_t *kept) {
-    __shared__ uint32_t s_pairs[2][4][GX_EMIT_STAGE]; /* [p/b][wave][slot] */
-    EmitStage E;
-    {
-        int wid = threadIdx.x >> 6;
-        E.s_p = s_pairs[0][wid];
-        E.s_b = s_pairs[1][wid];
-        E.cnt = 0;
-        E.lane = threadIdx.x & 63;
+/* ---- fused scan + probe kernel (gxop_join_probe_scan fast path) --------
+ * Grid-strides over the RAW rows in three wave-synchronous stages, so the
+ * emitted probe index is the raw row id and no projected column is
+ * materialized for rows the join drops.
+ *
+ * 1. Stream: a wave takes a tile of 64*R rows per iteration, row =
+ *    tile + r*64 + lane, so every load is a plain coalesced wave-wide
+ *    access whatever the column pointers' alignment. All R key loads and
+ *    the R loads of a predicate column are issued before the first use
+ *    (R x 768 B in flight per wave instead of 768 B), then the rows that
+ *    pass issue their bloom-word loads together.
+ * 2. Compact: rows that pass the predicates, have a non-NULL key and pass
+ *    the bloom are ballot-compacted into a per-wave LDS queue of
+ *    (raw row id, key).
+ * 3. Walk: whenever the queue holds >= 64 entries (and once at the end for
+ *    the rest) the wave pops 64, one per lane, and runs the bucket walk
+ *    (probe_key) on them: the random HBM line of the bucket is fetched
+ *    with every lane busy, not for the ~5 of 64 lanes that survive Q3's
+ *    predicate and bloom.
+ *
+ * Survivors of the predicates (not of the bloom) are counted per wave in a
+ * register and added to *kept once per wave. */
+#define GX_PS_R 2                          /* rows per lane per iteration */
+#define GX_PS_TILE (64 * GX_PS_R)          /* rows per wave per iteration */
+#define GX_PS_BLOCK_ROWS (256 * GX_PS_R)   /* rows per block per iteration */
+/* grid cap: one pass of the full grid covers 4096 * 256 * R rows
+ * (2,097,152 at R = 2); longer inputs grid-stride */
+#define GX_PS_GRID_CAP 4096
+/* queue: up to 63 carried entries + one iteration's worst case (64*R) */
+#define GX_PS_QCAP (64 + GX_PS_TILE)
+/* emit stage per wave: the largest that keeps queue (192 x 12 B) + stage
+ * (384 x 8 B) per wave, 21,504 B per block, at 7 blocks per CU inside the
+ * 160 KB of LDS, i.e. the 7 waves/SIMD the registers allow. Measured
+ * (profiles/README.md Round 5): the stage size moves the step more than R
+ * does, one atomicAdd on the pair counter per flush. */
+#define GX_PS_STAGE 384
+
+static inline int gx_ps_grid(int64_t n) {
+    int64_t g = (n + GX_PS_BLOCK_ROWS - 1) / GX_PS_BLOCK_ROWS;
+    if (g > GX_PS_GRID_CAP) g = GX_PS_GRID_CAP;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+/* AND the scan predicates into `pass` (bit r = row row0 + r*64) for the
+ * lane's R rows. Same semantics as scan_row_passes (a NULL value fails),
+ * but column by column: the R loads of a column go out back to back.
+ * Rows at or past n never load; their bits are already clear. */
+__device__ static inline uint32_t scan_rows_pass_wide(const ScanPreds &S,
+                                                      int64_t row0, int64_t n,
+                                                      uint32_t pass) {
+    for (int p = 0; p < S.n_preds; p++) {
+        const DevColView &c = S.pred_view[p];
+        const int32_t cmp = S.pred_cmp[p];
+        uint32_t ok = 0;
+        uint8_t nl[GX_PS_R];
+#pragma unroll
+        for (int r = 0; r < GX_PS_R; r++) {
+            const int64_t row = row0 + r * 64;
+            nl[r] = (c.has_nulls && row < n) ? c.nulls[row] : (uint8_t)0;
+        }
+        switch (c.type) {
+        case GX_I64: {
+            int64_t v[GX_PS_R];
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++) {
+                const int64_t row = row0 + r * 64;
+                v[r] = row < n ? ((const int64_t *)c.values)[row] : 0;
+            }
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++)
+                if (!nl[r] && cmp_i64(v[r], cmp, S.pred_i64[p])) ok |= 1u << r;
+            break; }
+        case GX_I32: {
+            int32_t v[GX_PS_R];
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++) {
+                const int64_t row = row0 + r * 64;
+                v[r] = row < n ? ((const int32_t *)c.values)[row] : 0;
+            }
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++)
+                if (!nl[r] && cmp_i64((int64_t)v[r], cmp, S.pred_i64[p]))
+                    ok |= 1u << r;
+            break; }
+        default: {
+            double v[GX_PS_R];
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++) {
+                const int64_t row = row0 + r * 64;
+                v[r] = row < n ? ((const double *)c.values)[row] : 0.0;
+            }
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++)
+                if (!nl[r] && cmp_f64(v[r], cmp, S.pred_f64[p])) ok |= 1u << r;
+            break; }
+        }
+        pass &= ok;
     }
+    return pass;
+}
+
+__global__ void __launch_bounds__(256)
+k_probe_scan(ProbeParams P, ScanPreds S, uint32_t *kept) {
+    __shared__ uint32_t s_pairs[2][4][GX_PS_STAGE]; /* [p/b][wave][slot] */
+    __shared__ int64_t s_qkey[4][GX_PS_QCAP];       /* [wave][queue slot] */
+    __shared__ uint32_t s_qrow[4][GX_PS_QCAP];
+    const int wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    EmitStage E;
+    E.s_p = s_pairs[0][wid];
+    E.s_b = s_pairs[1][wid];
+    E.cnt = 0;
+    E.lane = lane;
+    int64_t *qkey = s_qkey[wid];
+    uint32_t *qrow = s_qrow[wid];
+    uint32_t qcnt = 0;   /* wave-uniform */
     uint32_t n_kept = 0; /* wave-uniform */
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t base = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;;
-         base += stride) {
-        bool in = base < P.n_probe;
-        if (!__ballot(in)) break;
-        bool pass = in && scan_row_passes(S, base);
-        n_kept += (uint32_t)__popcll(__ballot(pass));
-        probe_one(P, E, pass, base);
+
+    const int64_t n = P.n_probe;
+    const DevColView &kc = P.probe_keys.col[0];
+    const int64_t *keys = (const int64_t *)kc.values;
+    const uint64_t *bloom = (const uint64_t *)P.bloom;
+    /* SLICE CONTAINS does not suit the column-wise form: per row instead */
+    bool wide = true;
+    for (int p = 0; p < S.n_preds; p++)
+        if (S.pred_view[p].type == GX_SLICE) wide = false;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+
+    const int64_t stride = (int64_t)gridDim.x * GX_PS_BLOCK_ROWS;
+    for (int64_t tile = blockIdx.x * (int64_t)GX_PS_BLOCK_ROWS +
+                        (int64_t)wid * GX_PS_TILE;
+         tile < n; tile += stride) { /* wave-uniform trip count */
+        const int64_t row0 = tile + lane;
+
+        /* 1. stream: keys (and their null bytes), then the predicates */
+        int64_t key[GX_PS_R];
+        uint32_t pass = 0, knull = 0;
+#pragma unroll
+        for (int r = 0; r < GX_PS_R; r++) {
+            const int64_t row = row0 + r * 64;
+            const bool in = row < n;
+            key[r] = in ? keys[row] : 0;
+            if (in) pass |= 1u << r;
+            if (kc.has_nulls && in && kc.nulls[row]) knull |= 1u << r;
+        }
+        if (wide) {
+            pass = scan_rows_pass_wide(S, row0, n, pass);
+        } else {
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++)
+                if (((pass >> r) & 1u) && !scan_row_passes(S, row0 + r * 64))
+                    pass &= ~(1u << r);
+        }
+#pragma unroll
+        for (int r = 0; r < GX_PS_R; r++)
+            n_kept += (uint32_t)__popcll(__ballot((pass >> r) & 1u));
+
+        /* bloom words of the live rows, all loads before the first test */
+        uint32_t live = pass & ~knull; /* a NULL key matches nothing */
+        if (bloom) {
+            uint64_t word[GX_PS_R], bits[GX_PS_R];
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++) {
+                const uint64_t x = bloom_mix(key[r]);
+                bits[r] = bloom_bits(x);
+                word[r] = ((live >> r) & 1u)
+                    ? bloom[bloom_word(x, P.bloom_mask)] : 0ull;
+            }
+#pragma unroll
+            for (int r = 0; r < GX_PS_R; r++)
+                if ((word[r] & bits[r]) != bits[r]) live &= ~(1u << r);
+        }
+
+        /* 2. compact the live rows into the wave's queue (slots qcnt..) */
+#pragma unroll
+        for (int r = 0; r < GX_PS_R; r++) {
+            const bool want = (live >> r) & 1u;
+            const unsigned long long m = __ballot(want);
+            if (want) {
+                const uint32_t at = qcnt + (uint32_t)__popcll(m & lt_mask);
+                qkey[at] = key[r];
+                qrow[at] = (uint32_t)(row0 + r * 64);
+            }
+            qcnt += (uint32_t)__popcll(m);
+        }
+
+        /* 3. dense walk: pop 64 from the tail while a full wave's worth is
+         * queued; at most 63 entries carry over, so qcnt never passes
+         * 63 + 64*R < GX_PS_QCAP */
+        while (qcnt >= 64) {
+            qcnt -= 64;
+            probe_key<GX_PS_STAGE>(P, E, true, qrow[qcnt + lane],
+                                   qkey[qcnt + lane]);
+        }
+    }
+    /* remainder */
+    if (qcnt) {
+        const bool active = (uint32_t)lane < qcnt;
+        probe_key<GX_PS_STAGE>(P, E, active, active ? qrow[lane] : 0u,
+                               active ? qkey[lane] : 0);
     }
     emit_flush(P, E);
-    if (E.lane == 0 && n_kept) atomicAdd(kept, n_kept);
+    if (lane == 0 && n_kept) atomicAdd(kept, n_kept);
 }
 
 /* Materialize the fused probe's pair list: probe-side output columns are
@@ -566,7 +740,7 @@ int probe_scan_fused(JoinOp *j, ScanOp *s, const gx_chunk *raw,
             HIP_OK(hipEventCreate(&j->ev1));
         }
         HIP_OK(hipEventRecord(j->ev0, stream));
-        hipLaunchKernelGGL(k_probe_scan, dim3(gx_grid(n)), dim3(256), 0,
+        hipLaunchKernelGGL(k_probe_scan, dim3(gx_ps_grid(n)), dim3(256), 0,
                            stream, P, S, (uint32_t *)j->d_meta.p + 2);
         HIP_OK(hipEventRecord(j->ev1, stream));
         uint32_t meta[3];
