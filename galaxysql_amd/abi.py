@@ -348,6 +348,15 @@ class GxLib:
             L.gxop_join_probe_scan.argtypes = [
                 C.c_void_p, C.c_void_p, C.POINTER(GxChunk),
                 C.POINTER(C.POINTER(GxResult)), C.POINTER(C.c_int64)]
+        # fused scan + group-join probe and the group-join's stats: HIP
+        # library only as well
+        self.has_groupjoin_probe_scan = hasattr(L, "gxop_groupjoin_probe_scan")
+        if self.has_groupjoin_probe_scan:
+            L.gxop_groupjoin_probe_scan.argtypes = [
+                C.c_void_p, C.c_void_p, C.POINTER(GxChunk),
+                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            L.gxop_groupjoin_get_stats.argtypes = [C.c_void_p,
+                                                   C.POINTER(GxJoinStats)]
         L.gxop_result_copy_col.argtypes = [C.POINTER(GxResult), C.c_int32,
                                            C.c_void_p, C.c_void_p]
         L.gxop_join_get_stats.argtypes = [C.c_void_p, C.POINTER(GxJoinStats)]

@@ -684,16 +684,27 @@ __device__ static inline void emit_flush(const ProbeParams &P, EmitStage &E) {
     E.cnt = 0;
 }
 
+/* What a full stage does with its pairs. The joins append them to the pair
+ * list; the group-join probe-scan (gxhip_scan.inc) accumulates them into
+ * the per-position records instead and writes no list. */
+struct PairListFlush {
+    __device__ inline void operator()(const ProbeParams &P,
+                                      EmitStage &E) const {
+        emit_flush(P, E);
+    }
+};
+
 /* STAGE = slots in this wave's LDS slice (>= 64: one call adds up to a
  * full wave of pairs). k_probe stages GX_EMIT_STAGE; the fused probe-scan
  * kernel, whose matches are sparse, a smaller one (gxhip_scan.inc). */
-template <uint32_t STAGE = GX_EMIT_STAGE>
+template <uint32_t STAGE = GX_EMIT_STAGE, class Flush = PairListFlush>
 __device__ static inline void emit_pair(const ProbeParams &P, EmitStage &E,
-                                        bool want, uint32_t pidx, uint32_t bpos) {
+                                        bool want, uint32_t pidx, uint32_t bpos,
+                                        const Flush &flush = Flush()) {
     unsigned long long m = __ballot(want);
     if (!m) return;
     uint32_t n = (uint32_t)__popcll(m);
-    if (E.cnt + n > STAGE) emit_flush(P, E);
+    if (E.cnt + n > STAGE) flush(P, E);
     if (want) {
         uint32_t at = E.cnt + (uint32_t)__popcll(m & ((1ull << E.lane) - 1ull));
         E.s_p[at] = pidx;
@@ -709,11 +720,12 @@ __device__ static inline void emit_pair(const ProbeParams &P, EmitStage &E,
  * lane has nothing to walk), ebase its slot index; e1 (lazily loaded, same
  * 64-B line) carries the overflow start. Shared by probe_one (k_probe)
  * and probe_key (the fused probe-scan kernel). */
-template <uint32_t STAGE = GX_EMIT_STAGE>
+template <uint32_t STAGE = GX_EMIT_STAGE, class Flush = PairListFlush>
 __device__ static inline void probe_walk(const ProbeParams &P, EmitStage &E,
                                          bool active, uint32_t i,
                                          int64_t want_key, JoinEntry e0,
-                                         uint64_t ebase, uint32_t end) {
+                                         uint64_t ebase, uint32_t end,
+                                         const Flush &flush = Flush()) {
     bool matched = false;
     uint32_t it = 0;
     uint32_t ovf0 = 0;
@@ -753,12 +765,12 @@ __device__ static inline void probe_walk(const ProbeParams &P, EmitStage &E,
             matched = true;
         }
         bool emit_now = is_match && !P.semi_join;
-        emit_pair<STAGE>(P, E, emit_now, i, bpos);
+        emit_pair<STAGE>(P, E, emit_now, i, bpos, flush);
     }
 
     /* post-row emissions (LEFT/RIGHT null rows, SEMI/ANTI rows) */
     bool want_null_row = active && P.outer_join && !P.build_outer && !matched;
-    emit_pair<STAGE>(P, E, want_null_row, i, 0xFFFFFFFFu);
+    emit_pair<STAGE>(P, E, want_null_row, i, 0xFFFFFFFFu, flush);
     if (P.semi_join) {
         bool want;
         if (P.join_type == GX_JOIN_SEMI) want = active && matched;
@@ -767,7 +779,7 @@ __device__ static inline void probe_walk(const ProbeParams &P, EmitStage &E,
             if (want && P.anti_null_col >= 0)
                 want = !col_is_null(P.anti_col, i);
         }
-        emit_pair<STAGE>(P, E, want, i, 0xFFFFFFFFu);
+        emit_pair<STAGE>(P, E, want, i, 0xFFFFFFFFu, flush);
     }
 }
 
@@ -830,9 +842,10 @@ __device__ static inline void probe_one(const ProbeParams &P, EmitStage &E,
 /* Fast-path (fast_i64) probe of an already-resolved (row id, key): the
  * caller has done the NULL-key and bloom tests. One lane per key, the
  * whole wave together, like probe_one. */
-template <uint32_t STAGE>
+template <uint32_t STAGE, class Flush = PairListFlush>
 __device__ static inline void probe_key(const ProbeParams &P, EmitStage &E,
-                                        bool active, uint32_t i, int64_t key) {
+                                        bool active, uint32_t i, int64_t key,
+                                        const Flush &flush = Flush()) {
     uint32_t end = 0;
     JoinEntry e0 = {0, 0, 0};
     uint64_t ebase = 0;
@@ -842,7 +855,7 @@ __device__ static inline void probe_key(const ProbeParams &P, EmitStage &E,
         e0 = P.table[ebase];
         end = e0.pad;
     }
-    probe_walk<STAGE>(P, E, active, i, key, e0, ebase, end);
+    probe_walk<STAGE>(P, E, active, i, key, e0, ebase, end, flush);
 }
 
 __global__ void k_probe(ProbeParams P) {

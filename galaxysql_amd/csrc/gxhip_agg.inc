@@ -172,91 +172,100 @@ struct AggAccumParams {
     unsigned long long *records;
 };
 
+/* One aggregate input value: `bits` holds an I64 value, a sign-extended I32
+ * or the bit pattern of an F64, `type` says which. COUNT(*) takes none. */
+struct AggVal {
+    unsigned long long bits;
+    int32_t type;
+    bool isnull;
+};
+
+__device__ static inline int64_t aggval_i64(const AggVal &v) {
+    return (int64_t)v.bits;
+}
+__device__ static inline double aggval_f64(const AggVal &v) {
+    return v.type == GX_F64 ? __builtin_bit_cast(double, v.bits)
+                            : (double)(int64_t)v.bits;
+}
+
+/* the value an aggregate of `func` reads from column c at row r (COUNT
+ * reads only the null flag; a NULL value is never loaded) */
+__device__ static inline AggVal agg_load(int32_t func, const DevColView &c,
+                                         int64_t r) {
+    AggVal v;
+    v.bits = 0;
+    v.type = c.type;
+    v.isnull = false;
+    if (func == GX_AGG_COUNT_ROW) return v;
+    v.isnull = col_is_null(c, r);
+    if (v.isnull || func == GX_AGG_COUNT_COL || c.type == GX_SLICE) return v;
+    v.bits = c.type == GX_I32
+        ? (unsigned long long)(int64_t)((const int32_t *)c.values)[r]
+        : ((const unsigned long long *)c.values)[r];
+    return v;
+}
+
+/* The read-modify-write of one aggregate on its record, for a value however
+ * it was obtained: a staged column (agg_apply) or a projection evaluated at
+ * a raw row (the group-join probe-scan). */
+__device__ static inline void agg_rmw(int32_t func, unsigned long long *rec,
+                                      int32_t val_off, int32_t seen_off,
+                                      const AggVal &v) {
+    unsigned long long *vp = rec + val_off;
+    if (func == GX_AGG_COUNT_ROW) {
+        atomicAdd(vp, 1ull);
+        return;
+    }
+    if (v.isnull) return;
+    switch (func) {
+    case GX_AGG_COUNT_COL:
+        atomicAdd(vp, 1ull);
+        break;
+    case GX_AGG_SUM_I64:
+        atomicAdd(vp, v.bits);
+        break;
+    case GX_AGG_SUM_I64N: /* null-init Sum: track seen */
+        atomicAdd(vp, v.bits);
+        if (seen_off >= 0) rec[seen_off] = 1ull;
+        break;
+    case GX_AGG_SUM_F64:
+        atomicAdd((double *)vp, aggval_f64(v));
+        rec[seen_off] = 1ull;
+        break;
+    case GX_AGG_MIN_I64:
+        atomic_min_i64((long long *)vp, (long long)aggval_i64(v));
+        rec[seen_off] = 1ull;
+        break;
+    case GX_AGG_MAX_I64:
+        atomic_max_i64((long long *)vp, (long long)aggval_i64(v));
+        rec[seen_off] = 1ull;
+        break;
+    case GX_AGG_MIN_F64:
+        atomic_jmin_f64(vp, __builtin_bit_cast(double, v.bits));
+        rec[seen_off] = 1ull;
+        break;
+    case GX_AGG_MAX_F64:
+        atomic_jmax_f64(vp, __builtin_bit_cast(double, v.bits));
+        rec[seen_off] = 1ull;
+        break;
+    case GX_AGG_BIT_AND: atomicAnd(vp, v.bits); break;
+    case GX_AGG_BIT_OR: atomicOr(vp, v.bits); break;
+    case GX_AGG_BIT_XOR: atomicXor(vp, v.bits); break;
+    case GX_AGG_AVG_F64:
+        /* state {sum f64, count u64}; the "seen" slot IS the count
+         * (atomicAdd, not the idempotent plain store) — NULL iff 0 */
+        atomicAdd((double *)vp, aggval_f64(v));
+        atomicAdd(rec + seen_off, 1ull);
+        break;
+    }
+}
+
 __device__ static inline void agg_apply(const AggAccumParams &P, uint32_t gid,
                                         int64_t r) {
     unsigned long long *rec = P.records + (size_t)gid * P.stride;
-    for (int a = 0; a < P.n_aggs; a++) {
-        const DevColView &c = P.input[a];
-        unsigned long long *vp = rec + P.val_off[a];
-        switch (P.func[a]) {
-        case GX_AGG_COUNT_ROW:
-            atomicAdd(vp, 1ull);
-            break;
-        case GX_AGG_COUNT_COL:
-            if (!col_is_null(c, r)) atomicAdd(vp, 1ull);
-            break;
-        case GX_AGG_SUM_I64:
-            if (!col_is_null(c, r)) {
-                int64_t v = c.type == GX_I32 ? (int64_t)((const int32_t *)c.values)[r]
-                                             : ((const int64_t *)c.values)[r];
-                atomicAdd(vp, (unsigned long long)v);
-            }
-            break;
-        case GX_AGG_SUM_I64N: /* null-init Sum: track seen */
-            if (!col_is_null(c, r)) {
-                int64_t v = c.type == GX_I32 ? (int64_t)((const int32_t *)c.values)[r]
-                                             : ((const int64_t *)c.values)[r];
-                atomicAdd(vp, (unsigned long long)v);
-                if (P.seen_off[a] >= 0) rec[P.seen_off[a]] = 1ull;
-            }
-            break;
-        case GX_AGG_SUM_F64:
-            if (!col_is_null(c, r)) {
-                double v = c.type == GX_F64 ? ((const double *)c.values)[r]
-                         : c.type == GX_I32 ? (double)((const int32_t *)c.values)[r]
-                                            : (double)((const int64_t *)c.values)[r];
-                atomicAdd((double *)vp, v);
-                rec[P.seen_off[a]] = 1ull;
-            }
-            break;
-        case GX_AGG_MIN_I64:
-        case GX_AGG_MAX_I64:
-            if (!col_is_null(c, r)) {
-                long long v = c.type == GX_I32 ? (long long)((const int32_t *)c.values)[r]
-                                               : ((const long long *)c.values)[r];
-                if (P.func[a] == GX_AGG_MIN_I64)
-                    atomic_min_i64((long long *)vp, v);
-                else
-                    atomic_max_i64((long long *)vp, v);
-                rec[P.seen_off[a]] = 1ull;
-            }
-            break;
-        case GX_AGG_MIN_F64:
-        case GX_AGG_MAX_F64:
-            if (!col_is_null(c, r)) {
-                double v = ((const double *)c.values)[r];
-                if (P.func[a] == GX_AGG_MIN_F64)
-                    atomic_jmin_f64(vp, v);
-                else
-                    atomic_jmax_f64(vp, v);
-                rec[P.seen_off[a]] = 1ull;
-            }
-            break;
-        case GX_AGG_BIT_AND:
-        case GX_AGG_BIT_OR:
-        case GX_AGG_BIT_XOR:
-            if (!col_is_null(c, r)) {
-                unsigned long long v = (unsigned long long)(
-                    c.type == GX_I32 ? (int64_t)((const int32_t *)c.values)[r]
-                                     : ((const int64_t *)c.values)[r]);
-                if (P.func[a] == GX_AGG_BIT_AND) atomicAnd(vp, v);
-                else if (P.func[a] == GX_AGG_BIT_OR) atomicOr(vp, v);
-                else atomicXor(vp, v);
-            }
-            break;
-        case GX_AGG_AVG_F64:
-            /* state {sum f64, count u64}; the "seen" slot IS the count
-             * (atomicAdd, not the idempotent plain store) — NULL iff 0 */
-            if (!col_is_null(c, r)) {
-                double v = c.type == GX_F64 ? ((const double *)c.values)[r]
-                         : c.type == GX_I32 ? (double)((const int32_t *)c.values)[r]
-                                            : (double)((const int64_t *)c.values)[r];
-                atomicAdd((double *)vp, v);
-                atomicAdd(rec + P.seen_off[a], 1ull);
-            }
-            break;
-        }
-    }
+    for (int a = 0; a < P.n_aggs; a++)
+        agg_rmw(P.func[a], rec, P.val_off[a], P.seen_off[a],
+                agg_load(P.func[a], P.input[a], r));
 }
 
 struct AggInsertParams {

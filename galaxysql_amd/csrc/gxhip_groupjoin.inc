@@ -14,6 +14,12 @@
  * INNER emits matched positions; LEFT emits all positions, the unmatched
  * ones as one null-row accumulation (buildNullRow: COUNT(*)=1,
  * COUNT(col)=0, SUM/MIN/MAX=NULL).
+ *
+ * Three table layouts, chosen at do_build: the CSR (any keys, null-safe),
+ * the wide CSR entries (one non-null I64 key, <= 2 COUNT/SUM_I64 aggs) and
+ * the plain joins' inline-bucket table + bloom (one non-null I64 key, any
+ * other aggregate list), which the fused probe-scan kernel of
+ * gxhip_scan.inc (gxop_groupjoin_probe_scan) walks.
  */
 
 namespace {
@@ -52,7 +58,18 @@ __global__ void k_gjw_expand(const JoinEntry *entries, int64_t n,
     }
 }
 
+/* add a lane's match count to the op's cumulative counter: summed across
+ * the wave first, so the counter takes one atomic per wave */
+__device__ static inline void gj_count_matches(unsigned long long *ctr,
+                                               uint32_t mine) {
+    for (int off = 32; off; off >>= 1)
+        mine += (uint32_t)__shfl_down((int)mine, off, 64);
+    if ((threadIdx.x & 63) == 0 && mine)
+        atomicAdd(ctr, (unsigned long long)mine);
+}
+
 struct GJWideProbeParams {
+    unsigned long long *matches;
     const uint32_t *starts;
     GJWideEntry *wide;
     uint32_t mask;
@@ -65,6 +82,7 @@ struct GJWideProbeParams {
 };
 
 __global__ void k_gjw_probe(GJWideProbeParams P) {
+    uint32_t n_match = 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < P.n;
          i += (int64_t)gridDim.x * blockDim.x) {
         /* build side has no null keys in wide mode; a null probe key
@@ -76,6 +94,7 @@ __global__ void k_gjw_probe(GJWideProbeParams P) {
         for (; it < end; it++) {
             GJWideEntry *w = &P.wide[it];
             if (w->key != want) continue;
+            n_match++;
             if (w->used == 0) atomicOr(&w->used, 1u);
             for (int a = 0; a < P.n_aggs; a++) {
                 switch (P.func[a]) {
@@ -98,6 +117,7 @@ __global__ void k_gjw_probe(GJWideProbeParams P) {
             }
         }
     }
+    gj_count_matches(P.matches, n_match);
 }
 
 /* scatter wide-entry state back into the per-position records + used
@@ -125,10 +145,12 @@ struct GJProbeParams {
     int fast_i64;
     KeyViews build_keys, probe_keys;
     uint32_t *used;
+    unsigned long long *matches;
     AggAccumParams A;
 };
 
 __global__ void k_gj_probe(GJProbeParams P) {
+    uint32_t n_match = 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < P.n;
          i += (int64_t)gridDim.x * blockDim.x) {
         uint32_t b = (uint32_t)gx_mix(P.hashes[i]) & P.mask;
@@ -146,12 +168,53 @@ __global__ void k_gj_probe(GJProbeParams P) {
                            rows_key_equal(P.build_keys, e.pos,
                                           P.probe_keys, i);
             if (!is_match) continue;
+            n_match++;
             uint32_t w = 1u << (e.pos & 31);
             if ((P.used[e.pos >> 5] & w) == 0)   /* test-then-set: one RMW */
                 atomicOr(&P.used[e.pos >> 5], w);
             agg_apply(P.A, e.pos, i);
         }
     }
+    gj_count_matches(P.matches, n_match);
+}
+
+/* Plain probe of an op whose build chose the inline-bucket table (see
+ * GroupJoinOp::do_build): one materialized probe row per lane, the bucket
+ * found from the key itself, no k_hash_rows pass. The build side carries
+ * no NULL key there, so a NULL probe key matches nothing. */
+struct GJInlineProbeParams {
+    const JoinEntry *table;
+    const JoinEntry *entries;   /* overflow runs */
+    uint32_t mask;
+    int64_t n;
+    DevColView probe_key;
+    uint32_t *used;
+    unsigned long long *matches;
+    AggAccumParams A;
+};
+
+__global__ void k_gj_probe_inline(GJInlineProbeParams P) {
+    uint32_t n_match = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < P.n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (col_is_null(P.probe_key, i)) continue;
+        const int64_t want = ((const int64_t *)P.probe_key.values)[i];
+        const uint64_t ebase =
+            (uint64_t)((uint32_t)gx_mix(gx_hash_i64(want)) & P.mask) * 4;
+        const uint32_t end = P.table[ebase].pad;
+        const uint32_t ovf0 = end > 4 ? P.table[ebase + 1].pad : 0u;
+        for (uint32_t it = 0; it < end; it++) {
+            const JoinEntry e = it < 4 ? P.table[ebase + it]
+                                       : P.entries[ovf0 + (it - 4)];
+            if (e.key != want) continue;
+            n_match++;
+            uint32_t w = 1u << (e.pos & 31);
+            if ((P.used[e.pos >> 5] & w) == 0)
+                atomicOr(&P.used[e.pos >> 5], w);
+            agg_apply(P.A, e.pos, i);
+        }
+    }
+    gj_count_matches(P.matches, n_match);
 }
 
 /* compact the positions whose used-bit is set (INNER emission list), with
@@ -224,6 +287,65 @@ __global__ void k_gj_emit(const unsigned long long *records, int32_t stride,
     }
 }
 
+/* One-kernel emission for fixed-width group columns: per emitted position
+ * the record (one random line) is read once and every key and aggregate
+ * column written from it. Same values as k_gather + k_gj_emit; an output
+ * whose nulls pointer is NULL (null-free source column, aggregate without
+ * a seen slot) skips the null store. */
+struct GJEmitParams {
+    const unsigned long long *records;
+    int32_t stride;
+    const uint32_t *idx;            /* NULL = positions 0..n-1 (LEFT) */
+    const uint32_t *used;
+    int count_row_null_row;
+    int64_t n;
+    int32_t n_keys, n_aggs;
+    DevColView key_src[GX_MAX_COLS];
+    int32_t key_words[GX_MAX_COLS]; /* element size in 4-B words */
+    void *key_vals[GX_MAX_COLS];
+    uint8_t *key_nulls[GX_MAX_COLS];
+    int32_t func[GX_MAX_COLS];
+    int32_t val_off[GX_MAX_COLS];
+    int32_t seen_off[GX_MAX_COLS];
+    void *agg_vals[GX_MAX_COLS];
+    uint8_t *agg_nulls[GX_MAX_COLS];
+};
+
+__global__ void k_gj_emit_all(GJEmitParams P) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < P.n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t g = P.idx ? P.idx[i] : (uint32_t)i;
+        for (int k = 0; k < P.n_keys; k++) {
+            const DevColView &src = P.key_src[k];
+            const bool nn = col_is_null(src, g);
+            if (P.key_nulls[k]) P.key_nulls[k][i] = nn;
+            const int32_t w = P.key_words[k];
+            const uint32_t *sv = (const uint32_t *)src.values + (size_t)g * w;
+            uint32_t *dv = (uint32_t *)P.key_vals[k] + (size_t)i * w;
+            for (int32_t j = 0; j < w; j++) dv[j] = nn ? 0u : sv[j];
+        }
+        const unsigned long long *rec = P.records + (size_t)g * P.stride;
+        const bool matched = (P.used[g >> 5] >> (g & 31)) & 1u;
+        for (int a = 0; a < P.n_aggs; a++) {
+            const int32_t func = P.func[a], so = P.seen_off[a];
+            const unsigned long long seen = so >= 0 ? rec[so] : 1ull;
+            const bool isnull = seen == 0ull;
+            if (P.agg_nulls[a]) P.agg_nulls[a][i] = isnull;
+            const unsigned long long v = isnull ? 0ull : rec[P.val_off[a]];
+            if (func == GX_AGG_AVG_F64) {
+                ((double *)P.agg_vals[a])[i] = isnull ? 0.0
+                    : __builtin_bit_cast(double, v) / (double)seen;
+            } else if (func == GX_AGG_COUNT_ROW) {
+                ((int64_t *)P.agg_vals[a])[i] = (int64_t)v +
+                    ((!matched && P.count_row_null_row) ? 1 : 0);
+            } else {
+                /* I64 results and F64 bit patterns alike */
+                ((unsigned long long *)P.agg_vals[a])[i] = v;
+            }
+        }
+    }
+}
+
 struct GroupJoinOp : gx_op {
     gx_groupjoin_cfg cfg;
     std::vector<gx_equi_key> keys;
@@ -231,12 +353,14 @@ struct GroupJoinOp : gx_op {
     std::vector<gx_agg_spec> aggs;
 
     /* last-allocated first (see DevBuf: destruction order and the pool) */
+    DevBuf d_accum;          /* GJAccum for the probe-scan kernel */
     DevBuf d_wide;
     DevBuf d_pn, d_ph, d_gj_tmp, d_cnt, d_gidx, d_used, d_records;
+    DevBuf d_meta;           /* u64 cumulative matches, u32 scan survivors */
     std::unique_ptr<JoinOp> jop; /* CSR build (null-safe hashing) */
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double kernel_ms = 0.0;
-    int64_t rows_total = 0;
+    int64_t rows_total = 0, probe_launches = 0, matches_total = 0;
     int32_t stride = 0;
     int32_t val_off[GX_MAX_COLS] = {0};
     int32_t seen_off[GX_MAX_COLS] = {0};
@@ -244,6 +368,13 @@ struct GroupJoinOp : gx_op {
     bool built = false, emitted = false;
     bool wide_ok = false;    /* cfg allows wide mode */
     bool wide = false;       /* chosen at do_build (needs null-free keys) */
+    /* inline-bucket mode, chosen at do_build: one I64 key, no NULL in the
+     * consumed key column (null-safe and plain equality then coincide) and
+     * not the wide mode. The inner JoinOp then builds the plain joins'
+     * inline-bucket table + bloom instead of the CSR, which is what the
+     * fused probe-scan walks (gxhip_scan.inc). */
+    bool inline_ok = false;  /* cfg allows it */
+    bool inline_tab = false;
 
     GroupJoinOp(const gx_groupjoin_cfg *c)
         : gx_op(OP_GROUPJOIN, c->device, c->stream), cfg(*c) {
@@ -271,6 +402,7 @@ struct GroupJoinOp : gx_op {
         jc.device = device;
         jc.stream = (uint64_t)stream;
         jc.expected_build_rows = c->expected_build_rows;
+        jc.enable_bloom = 1; /* acts on the inline-bucket build only */
         jop.reset(new JoinOp(&jc));
         jop->null_safe_keys = true;
 
@@ -308,6 +440,10 @@ struct GroupJoinOp : gx_op {
             wide_ok &= a.func == GX_AGG_COUNT_ROW ||
                        a.func == GX_AGG_COUNT_COL ||
                        a.func == GX_AGG_SUM_I64;
+        inline_ok = !wide_ok && keys.size() == 1 &&
+                    keys[0].unified_type == GX_I64 &&
+                    build_types[keys[0].outer_index] == GX_I64 &&
+                    probe_types[keys[0].inner_index] == GX_I64;
     }
     std::vector<gx_equi_key> swapped_keys;
 
@@ -319,8 +455,13 @@ struct GroupJoinOp : gx_op {
     int consume(const gx_chunk *ch) { return jop->consume(ch); }
 
     int do_build() {
+        inline_tab = inline_ok && jop->build.n_rows > 0 &&
+                     !jop->build.cols[jop->build_key_cols[0]].has_nulls;
+        jop->null_safe_keys = !inline_tab;
         if (jop->do_build()) return -1;
         const int64_t n = jop->build.n_rows;
+        if (d_meta.grow(16, stream)) return -1;
+        HIP_OK(hipMemsetAsync(d_meta.p, 0, 16, stream));
         if (n > 0) {
             if (d_records.grow((size_t)n * stride * 8, stream)) return -1;
             AggInitParams P;
@@ -358,19 +499,36 @@ struct GroupJoinOp : gx_op {
         StagedChunk st;
         if (st.stage(ch, stream)) return -1;
         const int64_t n = st.n_rows;
-        if (d_ph.grow((size_t)n * 4, stream) ||
-            d_pn.grow((size_t)n, stream)) return -1;
         KeyViews pk = jop->key_views_staged(st, jop->probe_key_cols);
-        hipLaunchKernelGGL(k_hash_rows, dim3(gx_grid(n)), dim3(256), 0,
-                           stream, pk, n, (int32_t *)d_ph.p,
-                           (uint8_t *)d_pn.p, 1 /* null_safe */);
+        if (!inline_tab) {
+            if (d_ph.grow((size_t)n * 4, stream) ||
+                d_pn.grow((size_t)n, stream)) return -1;
+            hipLaunchKernelGGL(k_hash_rows, dim3(gx_grid(n)), dim3(256), 0,
+                               stream, pk, n, (int32_t *)d_ph.p,
+                               (uint8_t *)d_pn.p, 1 /* null_safe */);
+        }
         if (!ev0) {
             HIP_OK(hipEventCreate(&ev0));
             HIP_OK(hipEventCreate(&ev1));
         }
-        if (wide) {
+        if (inline_tab) {
+            GJInlineProbeParams P;
+            std::memset(&P, 0, sizeof(P));
+            P.table = (const JoinEntry *)jop->d_table.p;
+            P.entries = (const JoinEntry *)jop->d_entries.p;
+            P.mask = jop->mask;
+            P.n = n;
+            P.probe_key = pk.col[0];
+            P.used = (uint32_t *)d_used.p;
+            P.matches = (unsigned long long *)d_meta.p;
+            fill_accum(P.A, st);
+            HIP_OK(hipEventRecord(ev0, stream));
+            hipLaunchKernelGGL(k_gj_probe_inline, dim3(gx_grid(n)), dim3(256),
+                               0, stream, P);
+        } else if (wide) {
             GJWideProbeParams W;
             std::memset(&W, 0, sizeof(W));
+            W.matches = (unsigned long long *)d_meta.p;
             W.starts = (const uint32_t *)jop->d_starts.p;
             W.wide = (GJWideEntry *)d_wide.p;
             W.mask = jop->mask;
@@ -398,27 +556,48 @@ struct GroupJoinOp : gx_op {
             P.build_keys = jop->key_views(jop->build, jop->build_key_cols);
             P.probe_keys = pk;
             P.used = (uint32_t *)d_used.p;
-            P.A.n_aggs = (int32_t)aggs.size();
-            P.A.stride = stride;
-            for (size_t a = 0; a < aggs.size(); a++) {
-                P.A.func[a] = aggs[a].func;
-                P.A.val_off[a] = val_off[a];
-                P.A.seen_off[a] = seen_off[a];
-                if (aggs[a].input_col >= 0)
-                    P.A.input[a] = st.views[aggs[a].input_col];
-            }
-            P.A.records = (unsigned long long *)d_records.p;
+            P.matches = (unsigned long long *)d_meta.p;
+            fill_accum(P.A, st);
             HIP_OK(hipEventRecord(ev0, stream));
             hipLaunchKernelGGL(k_gj_probe, dim3(gx_grid(n)), dim3(256), 0,
                                stream, P);
         }
         HIP_OK(hipEventRecord(ev1, stream));
-        /* also drains the probe before the staged chunk is freed */
+        /* the sync inside also drains the probe before the staged chunk is
+         * freed */
+        if (finish_probe(nullptr)) return -1;
+        rows_total += n;
+        return 0;
+    }
+
+    /* the aggregate half of a plain probe's params (zeroed by the caller) */
+    void fill_accum(AggAccumParams &A, const StagedChunk &st) const {
+        A.n_aggs = (int32_t)aggs.size();
+        A.stride = stride;
+        for (size_t a = 0; a < aggs.size(); a++) {
+            A.func[a] = aggs[a].func;
+            A.val_off[a] = val_off[a];
+            A.seen_off[a] = seen_off[a];
+            if (aggs[a].input_col >= 0)
+                A.input[a] = st.views[aggs[a].input_col];
+        }
+        A.records = (unsigned long long *)d_records.p;
+    }
+
+    /* after the probing kernel and ev1: fetch the counters, drain the
+     * stream, book the kernel time. *kept (may be NULL) receives the scan
+     * survivors the probe-scan kernel counted. */
+    int finish_probe(int64_t *kept) {
+        struct { unsigned long long matches; uint32_t kept, pad; } meta;
+        HIP_OK(hipMemcpyAsync(&meta, d_meta.p, 16, hipMemcpyDeviceToHost,
+                              stream));
         HIP_OK(hipStreamSynchronize(stream));
         float ms = 0;
         HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
         kernel_ms += ms;
-        rows_total += n;
+        probe_launches++;
+        matches_total = (int64_t)meta.matches;
+        if (kept) *kept = meta.kept;
         return 0;
     }
 
@@ -463,16 +642,62 @@ struct GroupJoinOp : gx_op {
         for (auto &sp : aggs) {
             switch (sp.func) {
             case GX_AGG_COUNT_ROW: case GX_AGG_COUNT_COL:
-            case GX_AGG_SUM_I64: case GX_AGG_MIN_I64: case GX_AGG_MAX_I64:
+            case GX_AGG_SUM_I64: case GX_AGG_SUM_I64N:
+            case GX_AGG_MIN_I64: case GX_AGG_MAX_I64:
             case GX_AGG_BIT_AND: case GX_AGG_BIT_OR: case GX_AGG_BIT_XOR:
                 otypes.push_back(GX_I64); break;
             default: otypes.push_back(GX_F64); break;
             }
         }
+        bool fixed_width = group_cols_.size() <= GX_MAX_COLS;
+        for (int32_t gc : group_cols_)
+            if (build_types[gc] == GX_SLICE) fixed_width = false;
+        if (fixed_width) {
+            /* one kernel writes every column; null-free outputs carry no
+             * nulls buffer (the scan and join convention) */
+            std::vector<uint8_t> null_free;
+            for (int32_t gc : group_cols_)
+                null_free.push_back(!jop->build.view(gc).has_nulls);
+            for (size_t a = 0; a < aggs.size(); a++)
+                null_free.push_back(seen_off[a] < 0);
+            auto h = alloc_result_cols(otypes, n_emit, device, stream,
+                                       &null_free);
+            if (!h) return -1;
+            GJEmitParams E;
+            std::memset(&E, 0, sizeof(E));
+            E.records = (const unsigned long long *)d_records.p;
+            E.stride = stride;
+            E.idx = idx;
+            E.used = (const uint32_t *)d_used.p;
+            E.count_row_null_row = (int)emit_all;
+            E.n = n_emit;
+            E.n_keys = (int32_t)group_cols_.size();
+            E.n_aggs = (int32_t)aggs.size();
+            size_t col = 0;
+            for (size_t k = 0; k < group_cols_.size(); k++, col++) {
+                E.key_src[k] = jop->build.view(group_cols_[k]);
+                E.key_words[k] =
+                    (int32_t)(gx_fixed_size(build_types[group_cols_[k]]) / 4);
+                E.key_vals[k] = h->bufs[col * 2].p;
+                E.key_nulls[k] = (uint8_t *)h->bufs[col * 2 + 1].p;
+            }
+            for (size_t a = 0; a < aggs.size(); a++, col++) {
+                E.func[a] = aggs[a].func;
+                E.val_off[a] = val_off[a];
+                E.seen_off[a] = seen_off[a];
+                E.agg_vals[a] = h->bufs[col * 2].p;
+                E.agg_nulls[a] = (uint8_t *)h->bufs[col * 2 + 1].p;
+            }
+            hipLaunchKernelGGL(k_gj_emit_all, dim3(gx_grid(n_emit)),
+                               dim3(256), 0, stream, E);
+            HIP_OK(hipStreamSynchronize(stream));
+            give_result(std::move(h), out);
+            return 0;
+        }
         auto h = alloc_result_cols(otypes, n_emit, device, stream);
         if (!h) return -1;
-        /* LEFT emits in position order: materialize an identity index for
-         * the gathers */
+        /* SLICE group columns: the per-column path. LEFT emits in position
+         * order: materialize an identity index for the gathers */
         if (emit_all) {
             if (d_gidx.grow((size_t)n_build * 4, stream)) return -1;
             hipLaunchKernelGGL(k_iota, dim3(gx_grid(n_build)), dim3(256), 0,
@@ -556,5 +781,14 @@ int gxop_groupjoin_next(gx_op *op, gx_result **out) {
     return static_cast<GroupJoinOp *>(op)->next(out);
 }
 int gxop_groupjoin_close(gx_op *op) { delete op; return 0; }
+int gxop_groupjoin_get_stats(gx_op *op, gx_join_stats *out) {
+    if (!op || op->kind != OP_GROUPJOIN || !out) { gx_set_err("not a groupjoin op"); return -1; }
+    GroupJoinOp *g = static_cast<GroupJoinOp *>(op);
+    out->probe_kernel_ms = g->kernel_ms;
+    out->probe_launches = g->probe_launches;
+    out->probe_rows = g->rows_total;
+    out->matches = g->matches_total;
+    return 0;
+}
 
 } /* extern "C" */

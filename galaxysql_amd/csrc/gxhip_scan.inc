@@ -162,10 +162,59 @@ __device__ static inline bool scan_row_passes(const ScanPreds &P, int64_t i) {
     return true;
 }
 
+/* The value of a register-sized projection at source row `src`: a COPY of
+ * an I64/I32/F64 column, REV_F64, REV_SCALED4 or Q9_AMOUNT4. The one place
+ * these expressions are computed: proj_store (k_scan, k_gather_proj) stores
+ * what this returns and the group-join probe-scan accumulates it, so all
+ * three are bit-identical. A NULL input gives isnull and the value the
+ * expression has over zeros. */
+__device__ static inline AggVal proj_value(int32_t op, const DevColView &a,
+                                           const DevColView &b,
+                                           const DevColView &cc,
+                                           const DevColView &dd, int64_t src) {
+    AggVal v;
+    v.bits = 0;
+    v.type = GX_I64;
+    switch (op) {
+    case GX_PROJ_COPY:
+        v.type = a.type;
+        v.isnull = col_is_null(a, src);
+        if (!v.isnull)
+            v.bits = a.type == GX_I32
+                ? (unsigned long long)(int64_t)((const int32_t *)a.values)[src]
+                : ((const unsigned long long *)a.values)[src];
+        break;
+    case GX_PROJ_REV_F64: {
+        v.type = GX_F64;
+        v.isnull = col_is_null(a, src) || col_is_null(b, src);
+        double av = v.isnull ? 0 : ((const double *)a.values)[src];
+        double bv = v.isnull ? 0 : ((const double *)b.values)[src];
+        v.bits = __builtin_bit_cast(unsigned long long, av * (1.0 - bv));
+        break; }
+    case GX_PROJ_REV_SCALED4: {
+        v.isnull = col_is_null(a, src) || col_is_null(b, src);
+        int64_t av = v.isnull ? 0 : ((const int64_t *)a.values)[src];
+        int64_t bv = v.isnull ? 0 : ((const int64_t *)b.values)[src];
+        v.bits = (uint64_t)av * (uint64_t)(100 - bv);
+        break; }
+    default: { /* GX_PROJ_Q9_AMOUNT4 */
+        v.isnull = col_is_null(a, src) || col_is_null(b, src) ||
+                   col_is_null(cc, src) || col_is_null(dd, src);
+        int64_t av = v.isnull ? 0 : ((const int64_t *)a.values)[src];
+        int64_t bv = v.isnull ? 0 : ((const int64_t *)b.values)[src];
+        int64_t cv = v.isnull ? 0 : ((const int64_t *)cc.values)[src];
+        int64_t dv = v.isnull ? 0 : ((const int64_t *)dd.values)[src];
+        v.bits = (unsigned long long)(
+            (int64_t)((uint64_t)av * (uint64_t)(100 - bv)) -
+            (int64_t)((uint64_t)cv * (uint64_t)dv * 100u));
+        break; }
+    }
+    return v;
+}
+
 /* Evaluate one projection at source row `src` and store it at output row
- * `at`. The one place a projected value is computed: k_scan and the fused
- * probe-scan gather both call it, so their values are bit-identical. SLICE
- * copies are not handled here (gathered in a post-pass). */
+ * `at`. k_scan and the fused probe-scan gather both call it. SLICE copies
+ * are not handled here (gathered in a post-pass). */
 __device__ static inline void proj_store(int32_t op, int32_t scale,
                                          const DevColView &a,
                                          const DevColView &b,
@@ -176,18 +225,25 @@ __device__ static inline void proj_store(int32_t op, int32_t scale,
     switch (op) {
     case GX_PROJ_COPY: {
         if (a.type == GX_SLICE) break; /* gathered post-pass */
-        bool nn = col_is_null(a, src);
-        if (out_nulls) out_nulls[at] = nn;
-        switch (a.type) {
-        case GX_I64: ((int64_t *)out_vals)[at] = nn ? 0 : ((const int64_t *)a.values)[src]; break;
-        case GX_I32: ((int32_t *)out_vals)[at] = nn ? 0 : ((const int32_t *)a.values)[src]; break;
-        case GX_F64: ((double *)out_vals)[at] = nn ? 0 : ((const double *)a.values)[src]; break;
-        case GX_DECIMAL:
+        if (a.type == GX_DECIMAL) {
+            bool nn = col_is_null(a, src);
+            if (out_nulls) out_nulls[at] = nn;
             for (int k = 0; k < 5; k++)
                 ((uint64_t *)out_vals)[(size_t)at * 5 + k] =
                     nn ? 0 : ((const uint64_t *)a.values)[src * 5 + k];
             break;
         }
+        AggVal v = proj_value(op, a, b, cc, dd, src);
+        if (out_nulls) out_nulls[at] = v.isnull;
+        if (a.type == GX_I32) ((int32_t *)out_vals)[at] = (int32_t)v.bits;
+        else ((unsigned long long *)out_vals)[at] = v.bits;
+        break; }
+    case GX_PROJ_REV_F64:
+    case GX_PROJ_REV_SCALED4:
+    case GX_PROJ_Q9_AMOUNT4: {
+        AggVal v = proj_value(op, a, b, cc, dd, src);
+        if (out_nulls) out_nulls[at] = v.isnull;
+        ((unsigned long long *)out_vals)[at] = v.bits;
         break; }
     case GX_PROJ_DEC_TO_SCALED: {
         bool nn = col_is_null(a, src);
@@ -204,33 +260,6 @@ __device__ static inline void proj_store(int32_t op, int32_t scale,
             for (int k = 0; k < 5; k++) ((uint64_t *)dst)[k] = 0;
         else
             scaled_to_dec40_dev(((const int64_t *)a.values)[src], scale, dst);
-        break; }
-    case GX_PROJ_REV_F64: {
-        bool nn = col_is_null(a, src) || col_is_null(b, src);
-        if (out_nulls) out_nulls[at] = nn;
-        double av = nn ? 0 : ((const double *)a.values)[src];
-        double bv = nn ? 0 : ((const double *)b.values)[src];
-        ((double *)out_vals)[at] = av * (1.0 - bv);
-        break; }
-    case GX_PROJ_REV_SCALED4: {
-        bool nn = col_is_null(a, src) || col_is_null(b, src);
-        if (out_nulls) out_nulls[at] = nn;
-        int64_t av = nn ? 0 : ((const int64_t *)a.values)[src];
-        int64_t bv = nn ? 0 : ((const int64_t *)b.values)[src];
-        ((int64_t *)out_vals)[at] =
-            (int64_t)((uint64_t)av * (uint64_t)(100 - bv));
-        break; }
-    case GX_PROJ_Q9_AMOUNT4: {
-        bool nn = col_is_null(a, src) || col_is_null(b, src) ||
-                  col_is_null(cc, src) || col_is_null(dd, src);
-        if (out_nulls) out_nulls[at] = nn;
-        int64_t av = nn ? 0 : ((const int64_t *)a.values)[src];
-        int64_t bv = nn ? 0 : ((const int64_t *)b.values)[src];
-        int64_t cv = nn ? 0 : ((const int64_t *)cc.values)[src];
-        int64_t dv = nn ? 0 : ((const int64_t *)dd.values)[src];
-        ((int64_t *)out_vals)[at] =
-            (int64_t)((uint64_t)av * (uint64_t)(100 - bv)) -
-            (int64_t)((uint64_t)cv * (uint64_t)dv * 100u);
         break; }
     }
 }
@@ -337,8 +366,14 @@ __device__ static inline uint32_t scan_rows_pass_wide(const ScanPreds &S,
     return pass;
 }
 
-__global__ void __launch_bounds__(256)
-k_probe_scan(ProbeParams P, ScanPreds S, uint32_t *kept) {
+/* The three stages, shared by k_probe_scan and the group-join's
+ * k_gj_probe_scan: they differ only in `flush`, what a full pair stage (and
+ * the last, partial one) does with its (raw row, build position) pairs. */
+template <class Flush>
+__device__ static inline void probe_scan_body(const ProbeParams &P,
+                                              const ScanPreds &S,
+                                              uint32_t *kept,
+                                              const Flush &flush) {
     __shared__ uint32_t s_pairs[2][4][GX_PS_STAGE]; /* [p/b][wave][slot] */
     __shared__ int64_t s_qkey[4][GX_PS_QCAP];       /* [wave][queue slot] */
     __shared__ uint32_t s_qrow[4][GX_PS_QCAP];
@@ -428,17 +463,88 @@ k_probe_scan(ProbeParams P, ScanPreds S, uint32_t *kept) {
         while (qcnt >= 64) {
             qcnt -= 64;
             probe_key<GX_PS_STAGE>(P, E, true, qrow[qcnt + lane],
-                                   qkey[qcnt + lane]);
+                                   qkey[qcnt + lane], flush);
         }
     }
     /* remainder */
     if (qcnt) {
         const bool active = (uint32_t)lane < qcnt;
         probe_key<GX_PS_STAGE>(P, E, active, active ? qrow[lane] : 0u,
-                               active ? qkey[lane] : 0);
+                               active ? qkey[lane] : 0, flush);
     }
-    emit_flush(P, E);
+    flush(P, E);
     if (lane == 0 && n_kept) atomicAdd(kept, n_kept);
+}
+
+__global__ void __launch_bounds__(256)
+k_probe_scan(ProbeParams P, ScanPreds S, uint32_t *kept) {
+    probe_scan_body(P, S, kept, PairListFlush());
+}
+
+/* ---- group-join probe-scan (gxop_groupjoin_probe_scan fast path) -------
+ * The same stream / compact / walk, but a full pair stage is ACCUMULATED,
+ * not written out: each lane takes one staged (raw row, build position),
+ * evaluates the aggregate-input projections at the raw row and applies them
+ * to records[position]. The group of a matched row IS its build position,
+ * so no pair list, no projected intermediate and no second hash table ever
+ * reach HBM, and every lane is busy during the random record RMWs just as
+ * the dense walk keeps every lane busy during the bucket fetch.
+ *
+ * The per-aggregate projection views are too large for the kernel-argument
+ * segment next to ProbeParams and ScanPreds (together past 4 KB), so they
+ * travel in a small device buffer read through wave-uniform loads. */
+struct GJAccum {
+    int32_t n_aggs;
+    int32_t stride;                 /* record size in u64s */
+    int32_t func[GX_MAX_COLS];
+    int32_t val_off[GX_MAX_COLS];
+    int32_t seen_off[GX_MAX_COLS];
+    int32_t op[GX_MAX_COLS];        /* the input's projection (unused for
+                                       COUNT(*)) */
+    DevColView a[GX_MAX_COLS];
+    DevColView b[GX_MAX_COLS];
+    DevColView c[GX_MAX_COLS];
+    DevColView d[GX_MAX_COLS];
+    unsigned long long *records;
+    uint32_t *used;
+    unsigned long long *matches;    /* cumulative (row, position) matches */
+};
+
+struct AccumFlush {
+    const GJAccum *A;
+    __device__ inline void operator()(const ProbeParams &,
+                                      EmitStage &E) const {
+        if (E.cnt == 0) return;
+        const GJAccum &G = *A;
+        for (uint32_t i = (uint32_t)E.lane; i < E.cnt; i += 64) {
+            const int64_t row = E.s_p[i];
+            const uint32_t pos = E.s_b[i];
+            const uint32_t w = 1u << (pos & 31);
+            if ((G.used[pos >> 5] & w) == 0) /* test-then-set: one RMW */
+                atomicOr(&G.used[pos >> 5], w);
+            unsigned long long *rec = G.records + (size_t)pos * G.stride;
+            for (int a = 0; a < G.n_aggs; a++) {
+                AggVal v;
+                v.bits = 0;
+                v.type = GX_I64;
+                v.isnull = false;
+                if (G.func[a] != GX_AGG_COUNT_ROW)
+                    v = proj_value(G.op[a], G.a[a], G.b[a], G.c[a], G.d[a],
+                                   row);
+                agg_rmw(G.func[a], rec, G.val_off[a], G.seen_off[a], v);
+            }
+        }
+        if (E.lane == 0) atomicAdd(G.matches, (unsigned long long)E.cnt);
+        E.cnt = 0;
+    }
+};
+
+__global__ void __launch_bounds__(256)
+k_gj_probe_scan(ProbeParams P, ScanPreds S, uint32_t *kept,
+                const GJAccum *A) {
+    AccumFlush flush;
+    flush.A = A;
+    probe_scan_body(P, S, kept, flush);
 }
 
 /* Materialize the fused probe's pair list: probe-side output columns are
@@ -811,9 +917,154 @@ int probe_scan_fused(JoinOp *j, ScanOp *s, const gx_chunk *raw,
     return -1; /* pair list still short after 4 resizes */
 }
 
+/* ---- fused scan + group-join probe (gxop_groupjoin_probe_scan) -------- */
+
+/* The fast path's conditions (gxop_hip.h): the op built the inline-bucket
+ * table (one I64 key, no NULL in the consumed key column), the key is a
+ * COPY of a raw I64 column, every aggregate input is a register-sized
+ * projection (proj_value), no DEC_TO_SCALED projection anywhere (its
+ * wide-DECIMAL fence must see every surviving row), device-resident input
+ * of fewer than 2^31 rows. */
+bool gj_probe_scan_fast_ok(const GroupJoinOp *g, const ScanOp *s,
+                           const gx_chunk *raw) {
+    if (!g->inline_tab || g->jop->pass_nothing) return false;
+    if (raw->n_rows <= 0 || (int64_t)raw->n_rows >= (INT64_C(1) << 31) ||
+        raw->n_blocks != (int32_t)s->input_types.size())
+        return false;
+    for (int32_t b = 0; b < raw->n_blocks; b++)
+        if (raw->blocks[b].mem != GX_MEM_DEVICE) return false;
+    const gx_proj &kp = s->projs[(size_t)g->jop->probe_key_cols[0]];
+    if (kp.op != GX_PROJ_COPY || s->input_types[kp.a] != GX_I64) return false;
+    for (auto &pr : s->projs)
+        if (pr.op == GX_PROJ_DEC_TO_SCALED) return false;
+    for (auto &sp : g->aggs) {
+        if (sp.input_col < 0) continue;
+        const gx_proj &pr = s->projs[(size_t)sp.input_col];
+        const int32_t t = s->out_types[(size_t)sp.input_col];
+        switch (pr.op) {
+        case GX_PROJ_COPY:
+            if (t != GX_I64 && t != GX_I32 && t != GX_F64) return false;
+            break;
+        case GX_PROJ_REV_F64: case GX_PROJ_REV_SCALED4:
+        case GX_PROJ_Q9_AMOUNT4:
+            break;
+        default:
+            return false;
+        }
+    }
+    return true;
+}
+
+int gj_probe_scan_fused(GroupJoinOp *g, ScanOp *s, const gx_chunk *raw,
+                        int64_t *n_kept) {
+    if (ensure_device(g->device)) return -1;
+    hipStream_t stream = g->stream;
+    JoinOp *j = g->jop.get();
+    StagedChunk st;
+    if (st.stage(raw, stream)) return -1; /* device-resident: zero copy */
+    const int64_t n = st.n_rows;
+    ScanPreds S;
+    if (s->fill_preds(S, st)) return -1;
+    const gx_proj &kp = s->projs[(size_t)j->probe_key_cols[0]];
+
+    ProbeParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.table = (const JoinEntry *)j->d_table.p;
+    P.entries = (const JoinEntry *)j->d_entries.p;
+    P.mask = j->mask;
+    P.n_probe = n;
+    P.bloom = (const uint32_t *)j->d_bloom.p;
+    P.bloom_mask = j->bloom_mask;
+    P.fast_i64 = 1;
+    P.probe_keys.n = 1;
+    P.probe_keys.col[0] = st.views[kp.a];
+    P.join_type = GX_JOIN_INNER; /* every match is a pair; LEFT only
+                                    changes the emission */
+    P.anti_null_col = -1;
+
+    GJAccum A;
+    std::memset(&A, 0, sizeof(A));
+    A.n_aggs = (int32_t)g->aggs.size();
+    A.stride = g->stride;
+    for (size_t a = 0; a < g->aggs.size(); a++) {
+        A.func[a] = g->aggs[a].func;
+        A.val_off[a] = g->val_off[a];
+        A.seen_off[a] = g->seen_off[a];
+        if (g->aggs[a].input_col < 0) continue;
+        const gx_proj &pr = s->projs[(size_t)g->aggs[a].input_col];
+        A.op[a] = pr.op;
+        A.a[a] = st.views[pr.a];
+        if (pr.op != GX_PROJ_COPY) A.b[a] = st.views[pr.b];
+        if (pr.op == GX_PROJ_Q9_AMOUNT4) {
+            A.c[a] = st.views[pr.c];
+            A.d[a] = st.views[pr.d];
+        }
+    }
+    A.records = (unsigned long long *)g->d_records.p;
+    A.used = (uint32_t *)g->d_used.p;
+    A.matches = (unsigned long long *)g->d_meta.p;
+    if (g->d_accum.grow(sizeof(A), stream)) return -1;
+    /* `A` outlives the copy: finish_probe drains the stream below */
+    HIP_OK(hipMemcpyAsync(g->d_accum.p, &A, sizeof(A), hipMemcpyHostToDevice,
+                          stream));
+    HIP_OK(hipMemsetAsync((char *)g->d_meta.p + 8, 0, 4, stream));
+    if (!g->ev0) {
+        HIP_OK(hipEventCreate(&g->ev0));
+        HIP_OK(hipEventCreate(&g->ev1));
+    }
+    HIP_OK(hipEventRecord(g->ev0, stream));
+    hipLaunchKernelGGL(k_gj_probe_scan, dim3(gx_ps_grid(n)), dim3(256), 0,
+                       stream, P, S, (uint32_t *)g->d_meta.p + 2,
+                       (const GJAccum *)g->d_accum.p);
+    HIP_OK(hipEventRecord(g->ev1, stream));
+    if (g->finish_probe(n_kept)) return -1;
+    g->rows_total += *n_kept;
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
+
+int gxop_groupjoin_probe_scan(gx_op *groupjoin, gx_op *scan,
+                              const gx_chunk *raw_chunk,
+                              int64_t *n_scan_kept, int64_t *n_matched) {
+    if (!groupjoin || groupjoin->kind != OP_GROUPJOIN) { gx_set_err("not a groupjoin op"); return -1; }
+    if (!scan || scan->kind != OP_SCAN) { gx_set_err("not a scan op"); return -1; }
+    if (!raw_chunk) { gx_set_err("groupjoin_probe_scan: null argument"); return -1; }
+    if (groupjoin->device != scan->device || groupjoin->stream != scan->stream) {
+        gx_set_err("groupjoin_probe_scan: group-join and scan must share "
+                   "device and stream");
+        return -1;
+    }
+    GroupJoinOp *g = static_cast<GroupJoinOp *>(groupjoin);
+    ScanOp *s = static_cast<ScanOp *>(scan);
+    std::lock_guard<std::mutex> lk(groupjoin->mu);
+    if (g->probe_types != s->out_types) {
+        gx_set_err("groupjoin_probe_scan: scan's projected types differ "
+                   "from the group-join's probe_types");
+        return -1;
+    }
+    if (!g->built) { gx_set_err("probe before build"); return -1; }
+    const int64_t before = g->matches_total;
+    int64_t kept = 0;
+    int rc;
+    if (gj_probe_scan_fast_ok(g, s, raw_chunk)) {
+        rc = gj_probe_scan_fused(g, s, raw_chunk, &kept);
+    } else {
+        /* composed sequence: scan, then probe with its projected chunk */
+        gx_result *t = nullptr;
+        rc = s->consume(raw_chunk, &t);
+        if (rc) return rc;
+        kept = t->chunk.n_rows;
+        rc = g->probe(&t->chunk);
+        gxop_result_release(t);
+    }
+    if (rc) return rc;
+    if (n_scan_kept) *n_scan_kept = kept;
+    if (n_matched) *n_matched = g->matches_total - before;
+    return 0;
+}
 
 int gxop_join_probe_scan(gx_op *join, gx_op *scan, const gx_chunk *raw_chunk,
                          gx_result **out, int64_t *n_scan_kept) {

@@ -296,6 +296,30 @@ class HashGroupJoinExec:
             self._lib.lib.gxop_groupjoin_probe(self._op, C.byref(gc)),
             "groupjoin_probe")
 
+    def probe_scan(self, scan, chunk_ref):
+        """Fused scan + group-join probe (gxop_groupjoin_probe_scan):
+        accumulate the rows of the raw chunk (a byref'd GxChunk) that pass
+        `scan`'s predicates. Returns (rows that passed the scan, matches
+        accumulated). Only on a library with has_groupjoin_probe_scan."""
+        kept = C.c_int64(0)
+        matched = C.c_int64(0)
+        self._lib.check(self._lib.lib.gxop_groupjoin_probe_scan(
+            self._op, scan._op, chunk_ref, C.byref(kept), C.byref(matched)),
+            "groupjoin_probe_scan")
+        return kept.value, matched.value
+
+    def stats(self):
+        """Cumulative probe stats, the fields of ParallelHashJoinExec.stats.
+        Only on a library with has_groupjoin_probe_scan."""
+        from .abi import GxJoinStats
+        s = GxJoinStats()
+        self._lib.check(
+            self._lib.lib.gxop_groupjoin_get_stats(self._op, C.byref(s)),
+            "groupjoin_get_stats")
+        return {"probe_kernel_ms": s.probe_kernel_ms,
+                "probe_launches": s.probe_launches,
+                "probe_rows": s.probe_rows, "matches": s.matches}
+
     def result_chunks(self):
         chunks = []
         while True:

@@ -23,7 +23,8 @@ from . import abi
 from .abi import GxResult
 from .chunk import I64, I32, F64, SLICE
 from .exchange import chunk_from_torch
-from .operators import ParallelHashJoinExec, HashAggExec, EquiJoinKey
+from .operators import (ParallelHashJoinExec, HashAggExec, HashGroupJoinExec,
+                        EquiJoinKey)
 
 CUST_TYPES = [I64]                       # c_custkey
 ORDERS_TYPES = [I64, I64, I32, I32]      # o_custkey, o_orderkey, o_orderdate, o_shippriority
@@ -113,6 +114,66 @@ def result_to_tensors(lib, res, types, device_t):
     return cols
 
 
+def _q3_groupjoin(lib, device, r1, n_orders_kept, lineitem, to_host,
+                  keep_results):
+    """join2 + GROUP BY of Q3 as ONE group-join, probed straight from the
+    unscanned lineitem (gxop_groupjoin_probe_scan).
+
+    Precondition, which a planner must check before choosing this plan: the
+    group key (l_orderkey, o_orderdate, o_shippriority) is the join key plus
+    columns of the consumed side, AND the consumed key is unique: orders are
+    keyed by their primary key o_orderkey, so one consumed position is one
+    group. With duplicate consumed keys a group-join emits one group per
+    position (the reference operator's own semantics), which is not GROUP
+    BY; the plain join + aggregate is the plan then.
+
+    Consumed side: join1's result (ORDERS_TYPES), key col 1 = o_orderkey;
+    the group columns [o_orderkey, o_orderdate, o_shippriority] equal the
+    aggregate's (l_orderkey = o_orderkey on every match). The aggregates
+    read the lineitem scan's projections [l_orderkey, revenue, cents]."""
+    gj = HashGroupJoinExec(
+        lib, abi.INNER, [EquiJoinKey(1, 0, I64)],
+        build_types=ORDERS_TYPES, probe_types=LINEITEM_TYPES,
+        group_cols=[1, 2, 3],
+        aggs=[(abi.SUM_F64, 1), (abi.SUM_I64, 2), (abi.COUNT_ROW, -1)],
+        device=device, expected_build_rows=n_orders_kept)
+    try:
+        if r1:
+            lib.check(lib.lib.gxop_groupjoin_consume(
+                gj._op, C.byref(r1.contents.chunk)), "groupjoin_consume")
+        gj.build_consume()
+        if r1:
+            lib.lib.gxop_result_release(r1)
+            r1 = None
+        lineitem.kept, n_joined = gj.probe_scan(lineitem.scan,
+                                                C.byref(lineitem.chunk))
+        j2_stats = gj.stats()
+        if to_host:
+            chunks = gj.result_chunks()
+            n_groups = sum(c.n_rows for c in chunks)
+        else:
+            chunks = []
+            n_groups = 0
+            while True:
+                out = C.POINTER(GxResult)()
+                lib.check(lib.lib.gxop_groupjoin_next(gj._op, C.byref(out)),
+                          "groupjoin_next")
+                if not out:
+                    break
+                n_groups += out.contents.chunk.n_rows
+                if keep_results is not None:
+                    keep_results.append(out)
+                else:
+                    lib.lib.gxop_result_release(out)
+        info = {"orders_kept": n_orders_kept, "joined_rows": n_joined,
+                "groups": n_groups, "join2_stats": j2_stats}
+        return chunks, info
+    finally:
+        if r1:
+            lib.lib.gxop_result_release(r1)
+        gj.close()
+
+
 def run_q3(lib, device, cust, orders, lineitem, expected_groups=0,
            to_host=True, reshuffle_by_orderkey=False, local_rank=0,
            keep_results=None):
@@ -139,6 +200,11 @@ def run_q3(lib, device, cust, orders, lineitem, expected_groups=0,
         j1.build_consume()
         r1 = _probe_src(lib, j1, orders, ORDERS_TYPES)
         n_orders_kept = r1.contents.chunk.n_rows if r1 else 0
+
+        if (isinstance(lineitem, _ScanSrc) and not reshuffle_by_orderkey
+                and getattr(lib, "has_groupjoin_probe_scan", False)):
+            return _q3_groupjoin(lib, device, r1, n_orders_kept, lineitem,
+                                 to_host, keep_results)
 
         # join2: INNER — build the surviving orders (key col 1 = o_orderkey),
         # probe lineitem on l_orderkey
