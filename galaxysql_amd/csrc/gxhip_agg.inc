@@ -260,6 +260,115 @@ __device__ static inline void agg_rmw(int32_t func, unsigned long long *rec,
     }
 }
 
+/* ---- transposed accumulate: one request per record line ----------------
+ * Atomics execute at the memory side, one request per 64-B line that an
+ * atomic INSTRUCTION touches (tools/micro_atomic.hip `records`, profiles/
+ * README.md Round 7): a lane that walks its record with agg_rmw sends one
+ * request per slot, while adjacent lanes of one instruction that cover the
+ * slots of one record send one between them. So for a record of up to
+ * GX_AGG_T_SLOTS u64 whose aggregates are all additive, 64 lanes that each
+ * hold one (row, record) contribution first say what they add to every slot
+ * (AggSlotOps), then agg_add_transposed turns the wave round: W = the power
+ * of two >= stride, W passes, lane L of pass i serves slot L % W of the
+ * contribution held by lane (L - L % W) + i. A pass is one f64 atomicAdd
+ * under the mask of f64 slots and one u64 atomicAdd under the mask of
+ * integer slots. The "seen" slot of a null-tracking SUM is ADDED 1 here
+ * (it rides in the integer instruction) where agg_rmw stores 1: every
+ * reader tests it against zero only, AVG's is a count either way. */
+#define GX_AGG_T_SLOTS 4
+
+__host__ __device__ static inline bool agg_func_additive(int32_t func) {
+    return func == GX_AGG_COUNT_ROW || func == GX_AGG_COUNT_COL ||
+           func == GX_AGG_SUM_I64 || func == GX_AGG_SUM_I64N ||
+           func == GX_AGG_SUM_F64 || func == GX_AGG_AVG_F64;
+}
+__host__ __device__ static inline bool agg_func_adds_f64(int32_t func) {
+    return func == GX_AGG_SUM_F64 || func == GX_AGG_AVG_F64;
+}
+
+/* what one contribution adds to each slot of its record: bit s of `skip`
+ * set = nothing (slot past the record, NULL input, idle lane) */
+struct AggSlotOps {
+    unsigned long long v[GX_AGG_T_SLOTS];
+    uint32_t skip;
+};
+
+__device__ static inline void agg_slot_ops_clear(AggSlotOps &o) {
+#pragma unroll
+    for (int s = 0; s < GX_AGG_T_SLOTS; s++) o.v[s] = 0ull;
+    o.skip = (1u << GX_AGG_T_SLOTS) - 1u;
+}
+
+/* enter one additive aggregate's value (agg_rmw's arithmetic, as operands) */
+__device__ static inline void agg_slot_ops_put(AggSlotOps &o, int32_t func,
+                                               int32_t val_off,
+                                               int32_t seen_off,
+                                               const AggVal &v) {
+    if (func != GX_AGG_COUNT_ROW && v.isnull) return;
+    unsigned long long x = v.bits;
+    if (func == GX_AGG_COUNT_ROW || func == GX_AGG_COUNT_COL) x = 1ull;
+    else if (agg_func_adds_f64(func))
+        x = __builtin_bit_cast(unsigned long long, aggval_f64(v));
+#pragma unroll
+    for (int s = 0; s < GX_AGG_T_SLOTS; s++) { /* no dynamic index: VGPRs */
+        if (s == val_off) { o.v[s] = x; o.skip &= ~(1u << s); }
+        if (s == seen_off) { o.v[s] = 1ull; o.skip &= ~(1u << s); }
+    }
+}
+
+/* Apply the wave's 64 contributions. Every lane of the wave calls it (an
+ * idle lane passes a cleared `o`); `width` (1, 2 or 4), `stride` and
+ * `f64_slots` (bit s = slot s takes an f64 add) are wave-uniform. Several
+ * lanes of one instruction may address one word: each add lands. */
+__device__ static inline void agg_add_transposed(unsigned long long *records,
+                                                 int32_t stride, int32_t width,
+                                                 uint32_t f64_slots,
+                                                 uint32_t rec_index,
+                                                 AggSlotOps o, int lane) {
+    unsigned long long skip_of[GX_AGG_T_SLOTS]; /* per slot, bit = lane */
+#pragma unroll
+    for (int s = 0; s < GX_AGG_T_SLOTS; s++)
+        skip_of[s] = __ballot((o.skip >> s) & 1u);
+    /* width x width transpose inside each group of `width` lanes: after it
+     * v[i] is what the group's lane i adds to THIS lane's slot */
+#pragma unroll
+    for (int b = 1; b < GX_AGG_T_SLOTS; b <<= 1) {
+        const bool hi = (lane & b) != 0;
+#pragma unroll
+        for (int r = 0; r < GX_AGG_T_SLOTS; r++) {
+            if ((r & b) == 0 && (r | b) < width) { /* wave-uniform */
+                const unsigned long long got =
+                    __shfl_xor(hi ? o.v[r] : o.v[r | b], b, 64);
+                if (hi) o.v[r] = got;
+                else o.v[r | b] = got;
+            }
+        }
+    }
+    const int slot = lane & (width - 1);
+    const int lane0 = lane - slot;
+    unsigned long long my_skip = skip_of[0];
+#pragma unroll
+    for (int s = 1; s < GX_AGG_T_SLOTS; s++)
+        if (slot == s) my_skip = skip_of[s];
+    const bool f64 = (f64_slots >> slot) & 1u;
+    /* every cross-lane read stands before the first divergent branch */
+    uint32_t at[GX_AGG_T_SLOTS];
+#pragma unroll
+    for (int i = 0; i < GX_AGG_T_SLOTS; i++)
+        at[i] = (uint32_t)__shfl((int)rec_index,
+                                 lane0 + (i < width ? i : 0), 64);
+#pragma unroll
+    for (int i = 0; i < GX_AGG_T_SLOTS; i++) {
+        if (i < width && !((my_skip >> (lane0 + i)) & 1ull)) {
+            unsigned long long *w = records + (size_t)at[i] * stride + slot;
+            if (f64)
+                atomicAdd((double *)w, __builtin_bit_cast(double, o.v[i]));
+            else
+                atomicAdd(w, o.v[i]);
+        }
+    }
+}
+
 __device__ static inline void agg_apply(const AggAccumParams &P, uint32_t gid,
                                         int64_t r) {
     unsigned long long *rec = P.records + (size_t)gid * P.stride;

@@ -188,7 +188,7 @@ struct GJInlineProbeParams {
     uint32_t mask;
     int64_t n;
     DevColView probe_key;
-    uint32_t *used;
+    uint32_t *used;             /* NULL: COUNT(*) says "matched" */
     unsigned long long *matches;
     AggAccumParams A;
 };
@@ -209,7 +209,7 @@ __global__ void k_gj_probe_inline(GJInlineProbeParams P) {
             if (e.key != want) continue;
             n_match++;
             uint32_t w = 1u << (e.pos & 31);
-            if ((P.used[e.pos >> 5] & w) == 0)
+            if (P.used && (P.used[e.pos >> 5] & w) == 0)
                 atomicOr(&P.used[e.pos >> 5], w);
             agg_apply(P.A, e.pos, i);
         }
@@ -217,10 +217,14 @@ __global__ void k_gj_probe_inline(GJInlineProbeParams P) {
     gj_count_matches(P.matches, n_match);
 }
 
-/* compact the positions whose used-bit is set (INNER emission list), with
- * per-wave LDS staging so the global counter sees 1 atomic per 512 hits */
-__global__ void k_gj_compact(const uint32_t *used, int64_t n, uint32_t *out,
-                             uint32_t *counter) {
+/* compact the matched positions (INNER emission list), with per-wave LDS
+ * staging so the global counter sees 1 atomic per 512 hits. Matched = the
+ * used-bit, or where the op keeps none (count_off >= 0) a non-zero
+ * COUNT(*) word of the position's record. */
+__global__ void k_gj_compact(const uint32_t *used,
+                             const unsigned long long *records,
+                             int32_t rec_stride, int32_t count_off,
+                             int64_t n, uint32_t *out, uint32_t *counter) {
     __shared__ uint32_t s_rows[4][GX_EMIT_STAGE];
     const int wid = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
@@ -242,7 +246,11 @@ __global__ void k_gj_compact(const uint32_t *used, int64_t n, uint32_t *out,
          i += stride) {
         bool active = i < n;
         if (!__ballot(active)) break;
-        bool want = active && (used[i >> 5] >> (i & 31)) & 1u;
+        bool want = false;
+        if (active)
+            want = count_off >= 0
+                ? records[(size_t)i * rec_stride + count_off] != 0ull
+                : (used[i >> 5] >> (i & 31)) & 1u;
         unsigned long long m = __ballot(want);
         uint32_t add = (uint32_t)__popcll(m);
         if (cnt + add > GX_EMIT_STAGE) flush();
@@ -260,13 +268,15 @@ __global__ void k_gj_compact(const uint32_t *used, int64_t n, uint32_t *out,
 __global__ void k_gj_emit(const unsigned long long *records, int32_t stride,
                           int32_t val_off, int32_t seen_off, int32_t func,
                           const uint32_t *idx, const uint32_t *used,
-                          int count_row_null_row, int64_t n,
+                          int32_t count_off, int count_row_null_row,
+                          int64_t n,
                           void *out_vals, uint8_t *out_nulls) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         uint32_t g = idx ? idx[i] : (uint32_t)i;
         const unsigned long long *rec = records + (size_t)g * stride;
-        bool matched = (used[g >> 5] >> (g & 31)) & 1u;
+        bool matched = count_off >= 0 ? rec[count_off] != 0ull
+                                      : (used[g >> 5] >> (g & 31)) & 1u;
         bool isnull = seen_off >= 0 && rec[seen_off] == 0ull;
         out_nulls[i] = isnull;
         bool f64 = func == GX_AGG_SUM_F64 || func == GX_AGG_MIN_F64 ||
@@ -297,6 +307,7 @@ struct GJEmitParams {
     int32_t stride;
     const uint32_t *idx;            /* NULL = positions 0..n-1 (LEFT) */
     const uint32_t *used;
+    int32_t count_off;              /* >= 0: matched = that word != 0 */
     int count_row_null_row;
     int64_t n;
     int32_t n_keys, n_aggs;
@@ -325,7 +336,9 @@ __global__ void k_gj_emit_all(GJEmitParams P) {
             for (int32_t j = 0; j < w; j++) dv[j] = nn ? 0u : sv[j];
         }
         const unsigned long long *rec = P.records + (size_t)g * P.stride;
-        const bool matched = (P.used[g >> 5] >> (g & 31)) & 1u;
+        const bool matched = P.count_off >= 0
+            ? rec[P.count_off] != 0ull
+            : (P.used[g >> 5] >> (g & 31)) & 1u;
         for (int a = 0; a < P.n_aggs; a++) {
             const int32_t func = P.func[a], so = P.seen_off[a];
             const unsigned long long seen = so >= 0 ? rec[so] : 1ull;
@@ -375,6 +388,12 @@ struct GroupJoinOp : gx_op {
      * fused probe-scan walks (gxhip_scan.inc). */
     bool inline_ok = false;  /* cfg allows it */
     bool inline_tab = false;
+    /* An INNER op in inline-bucket mode that has a COUNT(*) keeps no `used`
+     * bitmap: a position was matched exactly when that count is non-zero.
+     * count_off is the count's record slot then, -1 where the bitmap is
+     * kept (LEFT, the CSR and wide modes, no COUNT(*)). Set at do_build,
+     * before the first probe, so every probe kernel and the emission agree. */
+    int32_t count_off = -1;
 
     GroupJoinOp(const gx_groupjoin_cfg *c)
         : gx_op(OP_GROUPJOIN, c->device, c->stream), cfg(*c) {
@@ -458,6 +477,10 @@ struct GroupJoinOp : gx_op {
         inline_tab = inline_ok && jop->build.n_rows > 0 &&
                      !jop->build.cols[jop->build_key_cols[0]].has_nulls;
         jop->null_safe_keys = !inline_tab;
+        count_off = -1;
+        if (inline_tab && cfg.join_type == GX_JOIN_INNER)
+            for (size_t a = 0; a < aggs.size() && count_off < 0; a++)
+                if (aggs[a].func == GX_AGG_COUNT_ROW) count_off = val_off[a];
         if (jop->do_build()) return -1;
         const int64_t n = jop->build.n_rows;
         if (d_meta.grow(16, stream)) return -1;
@@ -519,7 +542,7 @@ struct GroupJoinOp : gx_op {
             P.mask = jop->mask;
             P.n = n;
             P.probe_key = pk.col[0];
-            P.used = (uint32_t *)d_used.p;
+            P.used = count_off >= 0 ? nullptr : (uint32_t *)d_used.p;
             P.matches = (unsigned long long *)d_meta.p;
             fill_accum(P.A, st);
             HIP_OK(hipEventRecord(ev0, stream));
@@ -626,7 +649,9 @@ struct GroupJoinOp : gx_op {
                 d_cnt.grow(4, stream)) return -1;
             HIP_OK(hipMemsetAsync(d_cnt.p, 0, 4, stream));
             hipLaunchKernelGGL(k_gj_compact, dim3(gx_grid(n_build)), dim3(256),
-                               0, stream, (const uint32_t *)d_used.p, n_build,
+                               0, stream, (const uint32_t *)d_used.p,
+                               (const unsigned long long *)d_records.p,
+                               stride, count_off, n_build,
                                (uint32_t *)d_gidx.p, (uint32_t *)d_cnt.p);
             uint32_t cnt = 0;
             HIP_OK(hipMemcpyAsync(&cnt, d_cnt.p, 4, hipMemcpyDeviceToHost,
@@ -669,6 +694,7 @@ struct GroupJoinOp : gx_op {
             E.stride = stride;
             E.idx = idx;
             E.used = (const uint32_t *)d_used.p;
+            E.count_off = count_off;
             E.count_row_null_row = (int)emit_all;
             E.n = n_emit;
             E.n_keys = (int32_t)group_cols_.size();
@@ -724,7 +750,8 @@ struct GroupJoinOp : gx_op {
                                stream, (const unsigned long long *)d_records.p,
                                stride, val_off[a], seen_off[a], aggs[a].func,
                                emit_all ? nullptr : idx,
-                               (const uint32_t *)d_used.p, (int)emit_all,
+                               (const uint32_t *)d_used.p, count_off,
+                               (int)emit_all,
                                n_emit, h->bufs[col * 2].p,
                                (uint8_t *)h->bufs[col * 2 + 1].p);
             col++;

@@ -506,8 +506,14 @@ struct GJAccum {
     DevColView c[GX_MAX_COLS];
     DevColView d[GX_MAX_COLS];
     unsigned long long *records;
-    uint32_t *used;
+    uint32_t *used;                 /* NULL: the op reads "matched" from its
+                                       COUNT(*) word (GroupJoinOp::count_off) */
     unsigned long long *matches;    /* cumulative (row, position) matches */
+    /* transposed accumulate (agg_add_transposed): the lane-group width, 0
+     * where the record is too wide or an aggregate is not additive, and
+     * the slots that take f64 adds */
+    int32_t t_width;
+    uint32_t t_f64;
 };
 
 struct AccumFlush {
@@ -516,11 +522,48 @@ struct AccumFlush {
                                       EmitStage &E) const {
         if (E.cnt == 0) return;
         const GJAccum &G = *A;
+        if (G.t_width) {
+            /* 64 staged pairs at a time, one per lane: every raw-column
+             * load (and the used word's) goes out before the first atomic,
+             * then the wave turns round so that a record's slots leave in
+             * adjacent lanes of one instruction */
+            for (uint32_t i0 = 0; i0 < E.cnt; i0 += 64) { /* wave-uniform */
+                const uint32_t i = i0 + (uint32_t)E.lane;
+                const bool active = i < E.cnt;
+                const int64_t row = active ? (int64_t)E.s_p[i] : 0;
+                const uint32_t pos = active ? E.s_b[i] : 0u;
+                const uint32_t w = 1u << (pos & 31);
+                uint32_t seen_w = w;
+                if (G.used && active) seen_w = G.used[pos >> 5];
+                AggSlotOps o;
+                agg_slot_ops_clear(o);
+#pragma unroll
+                for (int a = 0; a < GX_AGG_T_SLOTS; a++) {
+                    if (a >= G.n_aggs || !active) continue;
+                    AggVal v;
+                    v.bits = 0;
+                    v.type = GX_I64;
+                    v.isnull = false;
+                    if (G.func[a] != GX_AGG_COUNT_ROW)
+                        v = proj_value(G.op[a], G.a[a], G.b[a], G.c[a],
+                                       G.d[a], row);
+                    agg_slot_ops_put(o, G.func[a], G.val_off[a],
+                                     G.seen_off[a], v);
+                }
+                if ((seen_w & w) == 0) atomicOr(&G.used[pos >> 5], w);
+                agg_add_transposed(G.records, G.stride, G.t_width, G.t_f64,
+                                   pos, o, E.lane);
+            }
+            if (E.lane == 0) atomicAdd(G.matches, (unsigned long long)E.cnt);
+            E.cnt = 0;
+            return;
+        }
         for (uint32_t i = (uint32_t)E.lane; i < E.cnt; i += 64) {
             const int64_t row = E.s_p[i];
             const uint32_t pos = E.s_b[i];
             const uint32_t w = 1u << (pos & 31);
-            if ((G.used[pos >> 5] & w) == 0) /* test-then-set: one RMW */
+            /* test-then-set: one RMW */
+            if (G.used && (G.used[pos >> 5] & w) == 0)
                 atomicOr(&G.used[pos >> 5], w);
             unsigned long long *rec = G.records + (size_t)pos * G.stride;
             for (int a = 0; a < G.n_aggs; a++) {
@@ -1000,8 +1043,17 @@ int gj_probe_scan_fused(GroupJoinOp *g, ScanOp *s, const gx_chunk *raw,
             A.d[a] = st.views[pr.d];
         }
     }
+    bool additive = g->stride <= GX_AGG_T_SLOTS;
+    for (size_t a = 0; a < g->aggs.size(); a++)
+        additive = additive && agg_func_additive(g->aggs[a].func);
+    if (additive) {
+        A.t_width = g->stride <= 1 ? 1 : g->stride == 2 ? 2 : 4;
+        for (size_t a = 0; a < g->aggs.size(); a++)
+            if (agg_func_adds_f64(g->aggs[a].func))
+                A.t_f64 |= 1u << g->val_off[a];
+    }
     A.records = (unsigned long long *)g->d_records.p;
-    A.used = (uint32_t *)g->d_used.p;
+    A.used = g->count_off >= 0 ? nullptr : (uint32_t *)g->d_used.p;
     A.matches = (unsigned long long *)g->d_meta.p;
     if (g->d_accum.grow(sizeof(A), stream)) return -1;
     /* `A` outlives the copy: finish_probe drains the stream below */
