@@ -223,6 +223,40 @@ class GxScanCfg(C.Structure):
     ]
 
 
+class GxOrderBy(C.Structure):
+    """gx_order_by (include/gxop_hip.h). null_last mirrors
+    OrderByOption.nullLast and is ignored, as the reference comparator
+    ignores it (ExecUtils.getComparator)."""
+    _fields_ = [("col", C.c_int32), ("asc", C.c_int32),
+                ("null_last", C.c_int32)]
+
+
+class GxSortCfg(C.Structure):
+    _fields_ = [
+        ("n_cols", C.c_int32), ("types", C.POINTER(C.c_int32)),
+        ("n_order", C.c_int32), ("order", C.POINTER(GxOrderBy)),
+        ("offset", C.c_int64),
+        ("fetch", C.c_int64),
+        ("expected_rows", C.c_int64),
+        ("compact_rows", C.c_int64),
+        ("out_chunk_rows", C.c_int32),
+        ("device", C.c_int32),
+        ("stream", C.c_uint64),
+    ]
+
+
+class GxSortStats(C.Structure):
+    _fields_ = [
+        ("rows_consumed", C.c_int64),
+        ("rows_kept", C.c_int64),
+        ("compactions", C.c_int64),
+        ("used_select", C.c_int32),
+        ("select_passes", C.c_int32),
+        ("candidates", C.c_int64),
+        ("kernel_ms", C.c_double),
+    ]
+
+
 # Join types (gx_join_type)
 INNER, LEFT, RIGHT, SEMI, ANTI = 0, 1, 2, 3, 4
 # Comparisons (gx_cmp)
@@ -357,6 +391,19 @@ class GxLib:
                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             L.gxop_groupjoin_get_stats.argtypes = [C.c_void_p,
                                                    C.POINTER(GxJoinStats)]
+        # sort / top-N (ORDER BY ... LIMIT): HIP library only as well
+        self.has_sort = hasattr(L, "gxop_sort_create")
+        if self.has_sort:
+            L.gxop_sort_create.restype = C.c_void_p
+            L.gxop_sort_create.argtypes = [C.POINTER(GxSortCfg)]
+            L.gxop_sort_consume.argtypes = [C.c_void_p, C.POINTER(GxChunk)]
+            L.gxop_sort_build.argtypes = [C.c_void_p]
+            L.gxop_sort_next.argtypes = [C.c_void_p,
+                                         C.POINTER(C.POINTER(GxResult))]
+            L.gxop_sort_get_stats.argtypes = [C.c_void_p,
+                                              C.POINTER(GxSortStats)]
+            L.gxop_sort_close.restype = None
+            L.gxop_sort_close.argtypes = [C.c_void_p]
         L.gxop_result_copy_col.argtypes = [C.POINTER(GxResult), C.c_int32,
                                            C.c_void_p, C.c_void_p]
         L.gxop_join_get_stats.argtypes = [C.c_void_p, C.POINTER(GxJoinStats)]

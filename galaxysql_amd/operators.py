@@ -245,6 +245,124 @@ class HashAggExec:
             pass
 
 
+class OrderByOption:
+    """Mirror of OrderByOption (index, asc, nullLast). null_last is carried
+    and ignored, as ExecUtils.getComparator ignores it: NULL is the smallest
+    value, first under ASC and last under DESC."""
+
+    def __init__(self, col, asc=True, null_last=False):
+        self.col = col
+        self.asc = asc
+        self.null_last = null_last
+
+
+class SortExec:
+    """ORDER BY over the consumed chunks (SortExec.java; SortExecutorFactory),
+    with the HashAggExec lifecycle: consume_chunk* -> build_consume ->
+    result_chunks -> close. Stable: rows equal on every order column keep
+    arrival order. Only on a library with has_sort (the HIP library).
+
+    order_bys: OrderByOption instances or (col, asc) tuples."""
+
+    def __init__(self, lib, order_bys, input_types, offset=0, fetch=-1,
+                 expected_rows=0, compact_rows=0, out_chunk_rows=0,
+                 device=-1, stream=0):
+        if not getattr(lib, "has_sort", False):
+            raise RuntimeError(f"{lib.path} has no gxop_sort_* entry points")
+        self._lib = lib
+        obs = [o if isinstance(o, OrderByOption) else OrderByOption(*o)
+               for o in order_bys]
+        ob = (abi.GxOrderBy * max(1, len(obs)))()
+        for i, o in enumerate(obs):
+            ob[i] = abi.GxOrderBy(o.col, int(bool(o.asc)),
+                                  int(bool(o.null_last)))
+        it = (C.c_int32 * max(1, len(input_types)))(*input_types)
+        cfg = abi.GxSortCfg(n_cols=len(input_types), types=it,
+                            n_order=len(obs), order=ob, offset=offset,
+                            fetch=fetch, expected_rows=expected_rows,
+                            compact_rows=compact_rows,
+                            out_chunk_rows=out_chunk_rows, device=device,
+                            stream=stream)
+        self._keep = [ob, it, cfg]
+        self._op = lib.lib.gxop_sort_create(C.byref(cfg))
+        if not self._op:
+            raise RuntimeError(f"gxop_sort_create: {lib.error()}")
+
+    def consume_chunk(self, chunk: Chunk):
+        ka = []
+        gch = self._lib.to_gx_chunk(chunk, ka)
+        self.consume_raw(C.byref(gch))
+
+    def consume_raw(self, gx_chunk_ref):
+        """Consume a byref'd GxChunk (e.g. a device-resident gx_result's
+        chunk) without a host copy."""
+        self._lib.check(self._lib.lib.gxop_sort_consume(self._op,
+                                                        gx_chunk_ref),
+                        "sort_consume")
+
+    def build_consume(self):
+        self._lib.check(self._lib.lib.gxop_sort_build(self._op), "sort_build")
+
+    def result_chunks(self):
+        chunks = []
+        while True:
+            out = C.POINTER(GxResult)()
+            self._lib.check(self._lib.lib.gxop_sort_next(self._op,
+                                                         C.byref(out)),
+                            "sort_next")
+            if not out:
+                break
+            chunks.append(self._lib.result_to_chunk(out))
+        return chunks
+
+    def stats(self):
+        s = abi.GxSortStats()
+        self._lib.check(self._lib.lib.gxop_sort_get_stats(self._op,
+                                                          C.byref(s)),
+                        "sort_get_stats")
+        return {"rows_consumed": s.rows_consumed, "rows_kept": s.rows_kept,
+                "compactions": s.compactions,
+                "used_select": bool(s.used_select),
+                "select_passes": s.select_passes,
+                "candidates": s.candidates, "kernel_ms": s.kernel_ms}
+
+    def close(self):
+        if self._op:
+            self._lib.lib.gxop_sort_close(self._op)
+            self._op = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TopNExec(SortExec):
+    """ORDER BY ... LIMIT offset, fetch (SpilledTopNExec.java under a
+    LimitExec; TopNExecutorFactory / LimitExecFactory): keeps the best
+    offset + fetch rows while consuming, emits rows [offset, offset+fetch).
+    fetch = 0 passes nothing."""
+
+    def __init__(self, lib, order_bys, input_types, fetch, offset=0, **kw):
+        if fetch < 0:
+            raise ValueError("TopNExec needs fetch >= 0 (SortExec sorts all)")
+        super().__init__(lib, order_bys, input_types, offset=offset,
+                         fetch=fetch, **kw)
+
+
+def run_sort(lib, order_bys, input_types, input_chunks, **kw):
+    op = SortExec(lib, order_bys, input_types, **kw)
+    try:
+        for ch in input_chunks:
+            op.consume_chunk(ch)
+        op.build_consume()
+        out = op.result_chunks()
+        return out, op.stats()
+    finally:
+        op.close()
+
+
 class HashGroupJoinExec:
     """Fused join+agg (HashGroupJoinExec.java:186-447): consume the GROUP
     side, then feed probe chunks; one output row per (matched) consumed

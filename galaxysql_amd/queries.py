@@ -406,15 +406,24 @@ Q18_ORDERS_TYPES = [I64, I64, I64]       # o_orderkey, o_custkey, o_payload
 Q18_CUST_TYPES = [I64, I64]              # c_custkey, c_payload
 
 
+# final join output: c_custkey, c_payload, o_orderkey, o_custkey, o_payload,
+# l_orderkey, SUM(l_quantity)
+Q18_RESULT_TYPES = [I64] * 7
+
+
 def run_q18(lib, device, cust, orders, lineitem, having=300,
-            expected_groups=0, reshuffle_by_custkey=False):
+            expected_groups=0, reshuffle_by_custkey=False,
+            keep_results=None):
     """Q18: lineitem GROUP BY l_orderkey SUM(l_quantity)
     (the dominant operator: ~150M groups at SF100), HAVING sum > 300
     (~hundreds of survivors) via the library's own scan (GT predicate on
     each emitted device batch — the reference's FilterExec above the agg),
     then the tiny survivors join orders and customer.
 
-    Returns (n_final_rows, info)."""
+    Returns (n_final_rows, info). With a list as keep_results the final
+    device-resident join output (a gx_result pointer, columns
+    Q18_RESULT_TYPES) is appended to it instead of released, and the caller
+    releases it (q18_order_limit consumes it)."""
     import os
     import time
     import torch
@@ -521,7 +530,10 @@ def run_q18(lib, device, cust, orders, lineitem, having=300,
         r2 = _probe_tensors(lib, jb, list(cust), Q18_CUST_TYPES)
         n_final = r2.contents.chunk.n_rows if r2 else 0
         if r2:
-            lib.lib.gxop_result_release(r2)
+            if keep_results is not None:
+                keep_results.append(r2)
+            else:
+                lib.lib.gxop_result_release(r2)
     finally:
         jb.close()
 
@@ -529,6 +541,43 @@ def run_q18(lib, device, cust, orders, lineitem, having=300,
     info = {"groups": n_groups, "survivors": n_surv, "after_orders": n_r1,
             "final_rows": n_final, "agg_stats": agg_stats}
     return n_final, info
+
+
+def _order_limit(lib, device, results, types, order_bys, limit):
+    """ORDER BY ... LIMIT over device-resident result batches (gx_result
+    pointers; consumed in place, not released): the TopN + Limit a plan puts
+    above the aggregate. Returns the ordered rows as tuples."""
+    from .chunk import rows_of
+    from .operators import TopNExec
+    top = TopNExec(lib, order_bys, types, fetch=limit, device=device,
+                   expected_rows=sum(r.contents.chunk.n_rows
+                                     for r in results))
+    try:
+        for r in results:
+            top.consume_raw(C.byref(r.contents.chunk))
+        top.build_consume()
+        return rows_of(top.result_chunks())
+    finally:
+        top.close()
+
+
+def q3_order_limit(lib, device, results, limit=10):
+    """Q3's tail, ORDER BY revenue DESC, o_orderdate LIMIT 10, over the
+    keep_results batches of run_q3(..., to_host=False) (Q3_RESULT_TYPES:
+    revenue = the SUM_F64 column 3, o_orderdate = column 1). Only the
+    `limit` rows leave the device."""
+    return _order_limit(lib, device, results, Q3_RESULT_TYPES,
+                        [(3, False), (1, True)], limit)
+
+
+def q18_order_limit(lib, device, results, limit=100):
+    """Q18's tail, ORDER BY o_totalprice DESC, o_orderdate LIMIT 100, over
+    the keep_results of run_q18 (Q18_RESULT_TYPES). The synthetic orders
+    table carries one payload column: o_payload (column 4) stands for
+    o_totalprice, and o_orderkey (column 2) for o_orderdate as the
+    tie-breaker."""
+    return _order_limit(lib, device, results, Q18_RESULT_TYPES,
+                        [(4, False), (2, True)], limit)
 
 
 def gen_q18_numpy(rng, n_cust, n_orders, having_frac=0.0001):

@@ -80,6 +80,75 @@ int gxop_groupjoin_probe_scan(gx_op *groupjoin, gx_op *scan,
  * row, consumed position) matches accumulated */
 int gxop_groupjoin_get_stats(gx_op *groupjoin, gx_join_stats *out);
 
+/* ---- sort / top-N (ORDER BY ... [LIMIT offset, fetch]) ------------------ */
+
+/* SortExec / SpilledTopNExec / LimitExec in one operator: consume chunks,
+ * build (the buildConsume barrier), then drain the ordered rows
+ * [offset, offset + fetch) with gxop_sort_next.
+ *
+ * Order: the comparator of ExecUtils.getComparator (utils/ExecUtils.java:
+ * 451-490) over the order columns in turn -- both values NULL: next column;
+ * else type.compare, negated for DESC; first non-zero wins. NULL is the
+ * SMALLEST value (NumberType.compare, polardbx-optimizer/.../core/datatype/
+ * NumberType.java:110-127): first under ASC, last under DESC. I64/I32
+ * compare signed; F64 as Double.compareTo (-0.0 < +0.0, NaN above +Inf, all
+ * NaNs equal). Rows equal on every order column keep ARRIVAL order (consume
+ * order, then row order in the chunk): the operator is stable, which is one
+ * of the orders the reference's heap may produce.
+ *
+ * null_last mirrors OrderByOption.nullLast and is IGNORED, exactly as the
+ * reference comparator never consults it (ExecUtils.java:451-490 reads only
+ * index and asc); carried for fidelity like gx_equi_key.null_safe_equal.
+ *
+ * Order columns: I64, I32, F64. SLICE and DECIMAL order columns are
+ * rejected at create (string / decimal order keys are a follow-up); every
+ * type is carried as payload. */
+typedef struct gx_order_by {
+    int32_t col;        /* index into the input schema */
+    int32_t asc;        /* 1 = ASC, 0 = DESC */
+    int32_t null_last;  /* ignored, see above */
+} gx_order_by;
+
+typedef struct gx_sort_cfg {
+    int32_t n_cols;
+    const int32_t *types;      /* input = output schema */
+    int32_t n_order;           /* 1..8 */
+    const gx_order_by *order;
+    int64_t offset;            /* >= 0 */
+    int64_t fetch;             /* -1 = all rows (SortExec); 0 = pass nothing */
+    int64_t expected_rows;     /* hint, 0 = unknown */
+    int64_t compact_rows;      /* top-N: compact the store to its best
+                                  offset+fetch rows when it holds more than
+                                  max(this, 2*(offset+fetch)); 0 = default */
+    int32_t out_chunk_rows;    /* rows per emitted batch, 0 = one batch */
+    int32_t device;
+    uint64_t stream;
+} gx_sort_cfg;
+
+typedef struct gx_sort_stats {
+    int64_t rows_consumed;     /* rows passed to gxop_sort_consume */
+    int64_t rows_kept;         /* rows now in the device store */
+    int64_t compactions;       /* streaming top-N compactions run */
+    int32_t used_select;       /* last ordering: 1 = radix select then sort
+                                  of the candidates, 0 = full sort */
+    int32_t select_passes;     /* last ordering: histogram passes that ran */
+    int64_t candidates;        /* last ordering: rows handed to the sort */
+    double kernel_ms;          /* cumulative event time of the device work */
+} gx_sort_stats;
+
+/* NULL + gx_last_error on: n_order outside 1..8, an order col outside the
+ * schema or of SLICE/DECIMAL type, offset < 0, fetch < -1, device < 0.
+ * GX_TOPN_SELECT=0/1 in the environment at create forces the top-N path
+ * (full sort / radix select); unset, a size gate decides. */
+gx_op *gxop_sort_create(const gx_sort_cfg *cfg);
+/* host or device chunk; error once the store would pass 2^32-2 rows */
+int gxop_sort_consume(gx_op *op, const gx_chunk *chunk);
+int gxop_sort_build(gx_op *op);
+/* next ordered batch; *out = NULL when drained. Error before build. */
+int gxop_sort_next(gx_op *op, gx_result **out);
+int gxop_sort_get_stats(gx_op *op, gx_sort_stats *out);
+void gxop_sort_close(gx_op *op);
+
 #ifdef __cplusplus
 }
 #endif

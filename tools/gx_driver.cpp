@@ -76,6 +76,18 @@ struct GxApi {
     decltype(&gx_last_error)      last_error;
     decltype(&gxop_join_get_stats) join_stats;
     decltype(&gxop_abi_version)   abi_version;
+    /* HIP-library-only entry points (include/gxop_hip.h): bound when the
+     * library exports them, NULL otherwise (the CPU oracle) */
+    decltype(&gxop_sort_create)    sort_create = nullptr;
+    decltype(&gxop_sort_consume)   sort_consume = nullptr;
+    decltype(&gxop_sort_build)     sort_build = nullptr;
+    decltype(&gxop_sort_next)      sort_next = nullptr;
+    decltype(&gxop_sort_get_stats) sort_stats = nullptr;
+    decltype(&gxop_sort_close)     sort_close = nullptr;
+    bool has_sort() const {
+        return sort_create && sort_consume && sort_build && sort_next &&
+               sort_stats && sort_close;
+    }
 
     bool open(const char *path) {
         h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
@@ -133,6 +145,14 @@ struct GxApi {
         BIND(join_stats, gxop_join_get_stats)
         BIND(abi_version, gxop_abi_version)
 #undef BIND
+#define BIND_OPT(field, sym) field = (decltype(field))dlsym(h, #sym);
+        BIND_OPT(sort_create, gxop_sort_create)
+        BIND_OPT(sort_consume, gxop_sort_consume)
+        BIND_OPT(sort_build, gxop_sort_build)
+        BIND_OPT(sort_next, gxop_sort_next)
+        BIND_OPT(sort_stats, gxop_sort_get_stats)
+        BIND_OPT(sort_close, gxop_sort_close)
+#undef BIND_OPT
         return true;
     }
 };
@@ -866,6 +886,72 @@ static void t_fwindow(int device) {
 
 /* wire format: serialize -> deserialize -> reserialize must be identical
  * bytes, and the LongBlock golden frame must match the reference layout */
+/* Top-N, closed form: keys (i * 7919) % n over i = 0..n-1 are a permutation
+ * of 0..n-1 (7919 is prime and does not divide n), payload = i, pushed in
+ * several chunks. ORDER BY key ASC LIMIT offset, fetch must return keys
+ * offset..offset+fetch-1, DESC keys n-1-offset downwards, each with the
+ * payload i that solves i * 7919 = key (mod n). Skipped on a library
+ * without the sort entry points (the CPU oracle). */
+static void t_sort(int device) {
+    if (!api.has_sort()) {
+        std::printf("  sort/top-N: not exported by this library, skipped\n");
+        return;
+    }
+    const int64_t n = 100000, chunk = 7000, offset = 5, fetch = 40;
+    std::vector<int64_t> key(n), pay(n), row_of_key(n);
+    for (int64_t i = 0; i < n; i++) {
+        key[i] = (i * 7919) % n;
+        pay[i] = i;
+        row_of_key[key[i]] = i;
+    }
+    for (int asc = 1; asc >= 0; asc--) {
+        int32_t types[2] = {GX_I64, GX_I64};
+        gx_order_by ob{0, asc, 0};
+        gx_sort_cfg cfg{};
+        cfg.n_cols = 2; cfg.types = types;
+        cfg.n_order = 1; cfg.order = &ob;
+        cfg.offset = offset; cfg.fetch = fetch;
+        cfg.device = device;
+        gx_op *op = api.sort_create(&cfg);
+        CHECK(op, "sort_create");
+        if (!op) return;
+        for (int64_t lo = 0; lo < n; lo += chunk) {
+            const int64_t cnt = std::min(chunk, n - lo);
+            gx_block b[2] = {mk_i64(key.data() + lo), mk_i64(pay.data() + lo)};
+            gx_chunk c{(int32_t)cnt, 2, b};
+            CHECK(api.sort_consume(op, &c) == 0, "sort_consume");
+        }
+        CHECK(api.sort_build(op) == 0, "sort_build");
+        int64_t got = 0;
+        for (;;) {
+            gx_result *res = nullptr;
+            CHECK(api.sort_next(op, &res) == 0, "sort_next");
+            if (!res) break;
+            CHECK(api.result_to_host(res) == 0, "to_host");
+            for (int r = 0; r < res->chunk.n_rows; r++, got++) {
+                const int64_t want = asc ? offset + got : n - 1 - offset - got;
+                if (cell_i64(res, 0, r) != want ||
+                    cell_i64(res, 1, r) != row_of_key[want]) {
+                    CHECK(false, "top-N %s row %lld: key %lld payload %lld",
+                          asc ? "ASC" : "DESC", (long long)got,
+                          (long long)cell_i64(res, 0, r),
+                          (long long)cell_i64(res, 1, r));
+                    break;
+                }
+            }
+            api.result_release(res);
+        }
+        CHECK(got == fetch, "top-N rows %lld != %lld", (long long)got,
+              (long long)fetch);
+        gx_sort_stats st{};
+        CHECK(api.sort_stats(op, &st) == 0 && st.rows_consumed == n,
+              "sort stats");
+        api.sort_close(op);
+    }
+    std::printf("  sort/top-N: ASC + DESC, offset %lld fetch %lld of %lld ok\n",
+                (long long)offset, (long long)fetch, (long long)n);
+}
+
 static void t_serde() {
     int64_t vals[3] = {7, 0, -1};
     uint8_t nulls[3] = {0, 1, 0};
@@ -1079,6 +1165,7 @@ int main(int argc, char **argv) {
         t_window(device);
         t_fwindow(device);
         t_rank(device);
+        t_sort(device);
         t_serde();
         if (g_fail) {
             std::printf("SELFTEST FAILED: %d check(s)\n", g_fail);
