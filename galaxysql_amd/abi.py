@@ -287,6 +287,40 @@ SUM_I64N = 22
 DISTINCT_FUNCS = frozenset((COUNT_DISTINCT, SUM_I64_DISTINCT,
                             SUM_I64N_DISTINCT, SUM_F64_DISTINCT,
                             AVG_F64_DISTINCT))
+# Exact DECIMAL SUM / AVG (128-bit state, GX_DECIMAL output; gx_agg_func in
+# include/gxop.h). The input's decimal scale rides in the upper 16 bits of
+# the spec's func field (GX_AGG_WITH_SCALE): build specs with sum_dec(s) /
+# avg_dec(s). gxop_agg only.
+SUM_DEC, AVG_DEC = 28, 29
+DEC_FUNCS = frozenset((SUM_DEC, AVG_DEC))
+
+
+def with_scale(func, scale):
+    """GX_AGG_WITH_SCALE: func | scale << 16."""
+    return func | (int(scale) << 16)
+
+
+def sum_dec(scale):
+    """SUM_DEC over an input of decimal scale `scale` (0..9)."""
+    return with_scale(SUM_DEC, scale)
+
+
+def avg_dec(scale):
+    """AVG_DEC over an input of decimal scale `scale` (0..4); the result has
+    scale 4."""
+    return with_scale(AVG_DEC, scale)
+
+
+def base_func(func):
+    """The gx_agg_func of a spec's func field (scale stripped)."""
+    return func & 0xFFFF
+
+
+def func_scale(func):
+    """The decimal scale a spec's func field carries (0 for plain funcs)."""
+    return (func >> 16) & 0xFFFF
+
+
 _DISTINCT_OF = {COUNT_COL: COUNT_DISTINCT, SUM_I64: SUM_I64_DISTINCT,
                 SUM_I64N: SUM_I64N_DISTINCT, SUM_F64: SUM_F64_DISTINCT,
                 AVG_F64: AVG_F64_DISTINCT}

@@ -199,6 +199,61 @@ def dec40_decode(p, scale: int) -> int:
     return -v if isneg else v
 
 
+_DEC_WIDE_ERR = ("wide DECIMAL: needs more than 9 base-1e9 words (the 40-B "
+                 "DecimalStructure record holds 9)")
+
+
+def dec40_encode_wide(scaled: int, scale: int) -> bytes:
+    """General DecimalStructure record of scaled x 10^-scale, 0 <= scale <= 9
+    (DecimalTypeBase.java:61-65,101-102): base-1e9 integer words, most
+    significant first (at least one), then one fraction word holding the
+    fraction digits x 10^(9-scale); integers = 9 x integer words, fractions
+    = derivedFractions = scale, isNeg = 0 for zero. Byte-identical to
+    dec40_encode wherever that accepts the value; this is what SUM_DEC /
+    AVG_DEC emit."""
+    import struct
+    if not 0 <= scale <= 9:
+        raise ValueError(f"scale {scale} not supported (0..9)")
+    neg = scaled < 0
+    a = -scaled if neg else scaled
+    ip, rem = divmod(a, 10 ** scale)
+    words = []
+    while True:
+        ip, w = divmod(ip, 10 ** 9)
+        words.append(w)
+        if ip == 0:
+            break
+    words.reverse()
+    if len(words) > 8:
+        raise ValueError(_DEC_WIDE_ERR)
+    p = bytearray(40)
+    struct.pack_into(f"<{len(words) + 1}i", p, 0, *words,
+                     rem * 10 ** (9 - scale))
+    p[36] = 9 * len(words)
+    p[37] = scale
+    p[38] = scale
+    p[39] = 1 if neg and a else 0
+    return bytes(p)
+
+
+def dec40_decode_wide(p):
+    """(scaled, scale) of a general DecimalStructure record, scale = its
+    fractions byte: roundUp(integers) integer words, most significant first,
+    then roundUp(fractions) fraction words, the last one left-aligned."""
+    import struct
+    p = bytes(p)
+    integers, fractions, isneg = p[36], p[37], p[39]
+    iw, fw = (integers + 8) // 9, (fractions + 8) // 9
+    if iw + fw > 9:
+        raise ValueError(_DEC_WIDE_ERR)
+    w = struct.unpack_from(f"<{iw + fw}i", p, 0) if iw + fw else ()
+    v = 0
+    for x in w:
+        v = v * 10 ** 9 + x
+    v //= 10 ** (9 * fw - fractions)
+    return (-v if isneg else v), fractions
+
+
 def multiset(rows, f64_round=None, f64_sign_zero=False):
     """Canonical multiset of rows for order-insensitive parity compares
     (mirrors BaseExecTest.assertExecResultByRow, BaseExecTest.java:78-103).

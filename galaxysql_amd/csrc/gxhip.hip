@@ -29,6 +29,7 @@
  *   PartitioningExchanger.java:71-134
  */
 #include "gx_common.h"
+#include "gx_dec128.h"
 
 #include <algorithm>
 #include <cstdlib>

@@ -170,12 +170,19 @@ struct AggAccumParams {
     int32_t seen_off[GX_MAX_COLS];    /* -1 = always-valid agg */
     DevColView input[GX_MAX_COLS];    /* staged CURRENT-chunk value columns */
     unsigned long long *records;
+    /* SUM_DEC / AVG_DEC over a GX_DECIMAL column (read by the *_dec kernels
+     * only): the scale each record is brought to, the sticky fence word */
+    uint8_t dec_scale[GX_MAX_COLS];
+    uint32_t *dec_err;
 };
 
 /* One aggregate input value: `bits` holds an I64 value, a sign-extended I32
- * or the bit pattern of an F64, `type` says which. COUNT(*) takes none. */
+ * or the bit pattern of an F64, `type` says which. COUNT(*) takes none.
+ * `hi` is read by SUM_DEC / AVG_DEC only: the upper half of the 128-bit
+ * two's-complement value (an integer's sign extension, 0 or ~0). */
 struct AggVal {
     unsigned long long bits;
+    unsigned long long hi;
     int32_t type;
     bool isnull;
 };
@@ -188,12 +195,19 @@ __device__ static inline double aggval_f64(const AggVal &v) {
                             : (double)(int64_t)v.bits;
 }
 
+__host__ __device__ static inline bool agg_func_is_dec(int32_t func) {
+    return func == GX_AGG_SUM_DEC || func == GX_AGG_AVG_DEC;
+}
+
 /* the value an aggregate of `func` reads from column c at row r (COUNT
- * reads only the null flag; a NULL value is never loaded) */
+ * reads only the null flag; a NULL value is never loaded). DEC: the caller
+ * may hold a SUM_DEC / AVG_DEC and wants `hi` (see agg_apply). */
+template <bool DEC = false>
 __device__ static inline AggVal agg_load(int32_t func, const DevColView &c,
                                          int64_t r) {
     AggVal v;
     v.bits = 0;
+    v.hi = 0;
     v.type = c.type;
     v.isnull = false;
     if (func == GX_AGG_COUNT_ROW) return v;
@@ -202,12 +216,43 @@ __device__ static inline AggVal agg_load(int32_t func, const DevColView &c,
     v.bits = c.type == GX_I32
         ? (unsigned long long)(int64_t)((const int32_t *)c.values)[r]
         : ((const unsigned long long *)c.values)[r];
+    if (DEC) v.hi = (unsigned long long)((int64_t)v.bits >> 63);
+    return v;
+}
+
+/* SUM_DEC / AVG_DEC over a GX_DECIMAL column: decode the 40-B record (a
+ * strided read: up to 9 words + the 4 layout bytes) to a 128-bit integer at
+ * `scale`. A fenced value sets its bit in *err and reads as NULL. Only the
+ * *_dec kernels carry it (see agg_apply). */
+__device__ static inline AggVal agg_load_dec(const DevColView &c, int64_t r,
+                                             int scale, uint32_t *err) {
+    AggVal v;
+    v.bits = 0;
+    v.hi = 0;
+    v.type = GX_DECIMAL;
+    v.isnull = col_is_null(c, r);
+    if (v.isnull) return v;
+    gx_u128 mag;
+    bool neg;
+    const uint32_t fence = gx_dec40_to_u128(
+        (const uint8_t *)c.values + (size_t)r * 40, scale, &mag, &neg);
+    if (fence) {
+        atomicOr(err, fence);
+        v.isnull = true;
+        return v;
+    }
+    if (neg) mag = gx_u128_neg(mag);
+    v.bits = mag.lo;
+    v.hi = mag.hi;
     return v;
 }
 
 /* The read-modify-write of one aggregate on its record, for a value however
  * it was obtained: a staged column (agg_apply) or a projection evaluated at
- * a raw row (the group-join probe-scan). */
+ * a raw row (the group-join probe-scan). DEC = false compiles the SUM_DEC /
+ * AVG_DEC case out: the kernels of ops that cannot hold one (every op but a
+ * gxop_agg created with one) keep the code they had without it. */
+template <bool DEC = false>
 __device__ static inline void agg_rmw(int32_t func, unsigned long long *rec,
                                       int32_t val_off, int32_t seen_off,
                                       const AggVal &v) {
@@ -257,6 +302,23 @@ __device__ static inline void agg_rmw(int32_t func, unsigned long long *rec,
         atomicAdd((double *)vp, aggval_f64(v));
         atomicAdd(rec + seen_off, 1ull);
         break;
+    case GX_AGG_SUM_DEC:
+    case GX_AGG_AVG_DEC: {
+        if (!DEC) break;
+        /* state {lo, hi, seen | count}: a 128-bit two's-complement sum.
+         * The returning add on lo tells this lane whether ITS add wrapped
+         * lo; the carry joins the value's own upper half in one add on hi,
+         * skipped when that is zero (non-negative values, and negative
+         * ones whose add wraps lo). Addition mod 2^128 commutes and every
+         * wrap of lo is seen by exactly one returning atomic, so the state
+         * is exact under any interleaving. */
+        const unsigned long long old = atomicAdd(vp, v.bits);
+        const unsigned long long add_hi =
+            v.hi + ((old + v.bits) < old ? 1ull : 0ull);
+        if (add_hi != 0ull) atomicAdd(vp + 1, add_hi);
+        if (func == GX_AGG_SUM_DEC) rec[seen_off] = 1ull;
+        else atomicAdd(rec + seen_off, 1ull);
+        break; }
     }
 }
 
@@ -277,6 +339,8 @@ __device__ static inline void agg_rmw(int32_t func, unsigned long long *rec,
  * reader tests it against zero only, AVG's is a count either way. */
 #define GX_AGG_T_SLOTS 4
 
+/* SUM_DEC / AVG_DEC are NOT additive in this sense: their carry needs the
+ * returning add of agg_rmw, the transposed path sends non-returning ones */
 __host__ __device__ static inline bool agg_func_additive(int32_t func) {
     return func == GX_AGG_COUNT_ROW || func == GX_AGG_COUNT_COL ||
            func == GX_AGG_SUM_I64 || func == GX_AGG_SUM_I64N ||
@@ -369,12 +433,24 @@ __device__ static inline void agg_add_transposed(unsigned long long *records,
     }
 }
 
+/* DEC: the op has a SUM_DEC / AVG_DEC. Decided on the host, which then
+ * launches the *_dec twin of the kernel: the 128-bit case of agg_rmw, the
+ * high word of agg_load and the 40-B record decode exist only there, so the
+ * kernels every other op runs are compiled as if the funcs did not exist. */
+template <bool DEC = false>
 __device__ static inline void agg_apply(const AggAccumParams &P, uint32_t gid,
                                         int64_t r) {
     unsigned long long *rec = P.records + (size_t)gid * P.stride;
-    for (int a = 0; a < P.n_aggs; a++)
-        agg_rmw(P.func[a], rec, P.val_off[a], P.seen_off[a],
-                agg_load(P.func[a], P.input[a], r));
+    for (int a = 0; a < P.n_aggs; a++) {
+        if (DEC && P.input[a].type == GX_DECIMAL &&
+            agg_func_is_dec(P.func[a]))
+            agg_rmw<DEC>(P.func[a], rec, P.val_off[a], P.seen_off[a],
+                         agg_load_dec(P.input[a], r, P.dec_scale[a],
+                                      P.dec_err));
+        else
+            agg_rmw<DEC>(P.func[a], rec, P.val_off[a], P.seen_off[a],
+                         agg_load<DEC>(P.func[a], P.input[a], r));
+    }
 }
 
 struct AggInsertParams {
@@ -420,7 +496,8 @@ __device__ static inline bool agg_rows_equal(const AggInsertParams &P,
 
 #define GX_GID_PENDING 0xFFFFFFFFu
 
-__global__ void k_agg_insert(AggInsertParams P) {
+template <bool DEC>
+__device__ static inline void agg_insert_body(const AggInsertParams &P) {
     /* (see AggInsertParams.fuse_accum for the fused-accumulate contract) */
     /* Claims only — gid allocation is a SEPARATE compaction pass
      * (k_agg_gid_*): a per-claim atomicAdd on one ngroups word throttled
@@ -479,11 +556,19 @@ __global__ void k_agg_insert(AggInsertParams P) {
         }
         if (P.fuse_accum) {
             P.slot_of_row[r] = failed ? GX_SLOT_FAIL : slot;
-            if (!failed) agg_apply(P.A, slot, r);
+            if (!failed) agg_apply<DEC>(P.A, slot, r);
         } else {
             P.slot_of_row[r] = slot;
         }
     }
+}
+
+__global__ void k_agg_insert(AggInsertParams P) {
+    agg_insert_body<false>(P);
+}
+/* the same kernel for an op with a SUM_DEC / AVG_DEC (see agg_apply) */
+__global__ void k_agg_insert_dec(AggInsertParams P) {
+    agg_insert_body<true>(P);
 }
 
 /* gid compaction pass 1: count pending claims per slot tile (no hot word —
@@ -604,7 +689,7 @@ struct AggInitParams {
     unsigned long long *records;
     int32_t stride;
     int64_t from, to;
-    unsigned long long tmpl[2 * GX_MAX_COLS];
+    unsigned long long tmpl[3 * GX_MAX_COLS]; /* <= 3 slots per agg */
 };
 
 __global__ void k_agg_init(AggInitParams P) {
@@ -614,7 +699,8 @@ __global__ void k_agg_init(AggInitParams P) {
         P.records[P.from * P.stride + i] = P.tmpl[i % P.stride];
 }
 
-__global__ void k_agg_accumulate(AggAccumParams P) {
+template <bool DEC>
+__device__ static inline void agg_accumulate_body(const AggAccumParams &P) {
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < P.n;
          r += (int64_t)gridDim.x * blockDim.x) {
         uint32_t rec = 0;
@@ -625,8 +711,15 @@ __global__ void k_agg_accumulate(AggAccumParams P) {
              * experiment, profiles/README.md) */
             rec = P.slot_records ? P.slot_of_row[r]
                                  : P.slots[P.slot_of_row[r]].gid;
-        agg_apply(P, rec, r);
+        agg_apply<DEC>(P, rec, r);
     }
+}
+
+__global__ void k_agg_accumulate(AggAccumParams P) {
+    agg_accumulate_body<false>(P);
+}
+__global__ void k_agg_accumulate_dec(AggAccumParams P) {
+    agg_accumulate_body<true>(P);
 }
 
 /* Emission, one kernel for the whole result: each group's record (a random
@@ -643,6 +736,7 @@ struct AggEmitParams {
     int32_t func[GX_MAX_COLS];
     int32_t val_off[GX_MAX_COLS];
     int32_t seen_off[GX_MAX_COLS];
+    uint8_t dec_scale[GX_MAX_COLS];  /* SUM_DEC / AVG_DEC: input scale */
     void *out_vals[GX_MAX_COLS];
     uint8_t *out_nulls[GX_MAX_COLS];
     int32_t n_keys;                /* 0 = key columns gathered separately */
@@ -681,6 +775,28 @@ __global__ void k_agg_emit(AggEmitParams P) {
             const int32_t func = P.func[a], seen_off = P.seen_off[a];
             bool isnull = seen_off >= 0 && rec[seen_off] == 0ull;
             P.out_nulls[a][g] = isnull;
+            if (agg_func_is_dec(func)) {
+                /* 40-B DecimalBlock record of the 128-bit state; AVG
+                 * divides |sum| by the count, half-up at scale 4 */
+                uint8_t *dst = (uint8_t *)P.out_vals[a] + (size_t)g * 40;
+                if (isnull) { /* zero record, as every NULL DECIMAL */
+                    for (int k = 0; k < 5; k++)
+                        ((unsigned long long *)dst)[k] = 0ull;
+                    continue;
+                }
+                gx_u128 mag;
+                mag.lo = rec[P.val_off[a]];
+                mag.hi = rec[P.val_off[a] + 1];
+                const bool neg = (mag.hi >> 63) != 0ull;
+                if (neg) mag = gx_u128_neg(mag);
+                int scale = P.dec_scale[a];
+                if (func == GX_AGG_AVG_DEC) {
+                    mag = gx_dec_avg4(mag, rec[seen_off], scale);
+                    scale = 4;
+                }
+                gx_u128_to_dec40(mag, neg, scale, dst);
+                continue;
+            }
             bool f64 = func == GX_AGG_SUM_F64 || func == GX_AGG_MIN_F64 ||
                        func == GX_AGG_MAX_F64 || func == GX_AGG_AVG_F64;
             unsigned long long v = isnull ? 0ull : rec[P.val_off[a]];
@@ -872,6 +988,11 @@ static inline int32_t agg_distinct_base(int32_t f) {
 static inline bool gx_agg_is_distinct(int32_t f) {
     return agg_distinct_base(f) >= 0;
 }
+/* SUM_DEC / AVG_DEC, with or without a scale in the upper 16 bits: gxop_agg
+ * only as well (the other ops' emit kernels write 8-B values) */
+static inline bool gx_agg_is_dec(int32_t f) {
+    return agg_func_is_dec(f & 0xFFFF);
+}
 
 /* host side of one distinct set (one per distinct input column) */
 struct DistSet {
@@ -898,6 +1019,7 @@ struct AggOp : gx_op {
     /* device buffers, last-allocated first (see DevBuf: destruction order
      * and the pool); d_slots / d_records, d_hashes / d_slotidx and
      * d_krow_of_gid / d_slot_of_gid share a size class */
+    DevBuf d_decerr;            /* DECIMAL-input fence word (sticky bits) */
     std::vector<DistSet> dsets; /* one per distinct input column */
     DevBuf d_dstatus;           /* per chunk row: distinct pass status */
     DevBuf d_slot_of_gid;      /* slot mode: record index per gid */
@@ -907,10 +1029,16 @@ struct AggOp : gx_op {
     DevStore keystore;         /* appended group-key columns (for emit) */
     bool slot_records = false; /* records indexed by slot (narrow state) */
     bool tmpl_zero = true;     /* identity record is all zero bits */
+    /* SUM_DEC / AVG_DEC: aggs[] holds the base func, the scale that rode in
+     * the spec's upper 16 bits is split off here once */
+    uint8_t dec_scale[GX_MAX_COLS] = {0};
+    bool has_dec = false;       /* consume launches the *_dec kernels */
+    bool has_dec_input = false; /* one of them reads a GX_DECIMAL column:
+                                   consume reads the fence word back */
     int32_t stride = 0;        /* record size in u64s */
     int32_t val_off[GX_MAX_COLS] = {0};
     int32_t seen_off[GX_MAX_COLS] = {0};
-    unsigned long long tmpl[2 * GX_MAX_COLS] = {0};
+    unsigned long long tmpl[3 * GX_MAX_COLS] = {0};
     int64_t n_slots = 0;
     uint32_t mask = 0;
     uint32_t n_groups_host = 0;
@@ -927,6 +1055,14 @@ struct AggOp : gx_op {
         input_types.assign(c->input_types, c->input_types + c->n_input_cols);
         aggs.assign(c->aggs, c->aggs + c->n_aggs);
         is_distinct.assign(aggs.size(), 0);
+        for (size_t a = 0; a < aggs.size(); a++) {
+            dec_scale[a] = (uint8_t)((uint32_t)aggs[a].func >> 16);
+            aggs[a].func &= 0xFFFF;
+            if (!agg_func_is_dec(aggs[a].func)) continue;
+            has_dec = true;
+            if (input_types[aggs[a].input_col] == GX_DECIMAL)
+                has_dec_input = true;
+        }
         for (size_t a = 0; a < aggs.size(); a++) {
             int32_t base = agg_distinct_base(aggs[a].func);
             if (base < 0) continue;
@@ -964,8 +1100,9 @@ struct AggOp : gx_op {
                      && group_cols_.size() >= 2;
         keystore.init((int32_t)key_types.size(), key_types.data(), stream);
 
-        /* AoS record layout: one u64 value slot per agg (+ one u64 seen
-         * slot for null-tracking aggs), identity-initialized. */
+        /* AoS record layout: one u64 value slot per agg (two for the 128-bit
+         * SUM_DEC / AVG_DEC sum) + one u64 seen slot for null-tracking aggs
+         * (AVG's is its count), identity-initialized. */
         int32_t off = 0;
         for (size_t a = 0; a < aggs.size(); a++) {
             val_off[a] = off;
@@ -978,6 +1115,8 @@ struct AggOp : gx_op {
             default: tmpl[off] = 0ull; break;
             }
             off++;
+            if (agg_func_is_dec(aggs[a].func)) /* {lo, hi}: hi follows lo */
+                tmpl[off++] = 0ull;
             bool tracks_null = !(aggs[a].func == GX_AGG_COUNT_ROW ||
                                  aggs[a].func == GX_AGG_COUNT_COL ||
                                  aggs[a].func == GX_AGG_SUM_I64 ||
@@ -1064,8 +1203,10 @@ struct AggOp : gx_op {
             A.func[a] = aggs[a].func;
             A.val_off[a] = val_off[a];
             A.seen_off[a] = seen_off[a];
+            A.dec_scale[a] = dec_scale[a];
             if (aggs[a].input_col >= 0) A.input[a] = st.views[aggs[a].input_col];
         }
+        A.dec_err = (uint32_t *)d_decerr.p;
     }
 
     /* any group-key column has carried a NULL so far (sticky per column;
@@ -1240,6 +1381,10 @@ struct AggOp : gx_op {
             HIP_OK(hipEventCreate(&ev1));
         }
         HIP_OK(hipEventRecord(ev0, stream));
+        if (has_dec_input && !d_decerr.p) {
+            if (d_decerr.grow(4, stream)) return -1;
+            HIP_OK(hipMemsetAsync(d_decerr.p, 0, 4, stream));
+        }
 
         const bool no_group_by = group_cols_.empty();
         int64_t base_krow = keystore.n_rows;
@@ -1318,7 +1463,9 @@ struct AggOp : gx_op {
                 if (slot_records)
                     fill_accum_params(IP.A, st); /* records ptr per attempt
                                                     (rehash reallocates) */
-                hipLaunchKernelGGL(k_agg_insert, dim3(gx_grid(n)), dim3(256), 0,
+                auto k_insert = slot_records && has_dec ? k_agg_insert_dec
+                                                        : k_agg_insert;
+                hipLaunchKernelGGL(k_insert, dim3(gx_grid(n)), dim3(256), 0,
                                    stream, IP);
                 uint32_t ovf = 0;
                 HIP_OK(hipMemcpyAsync(&ovf, (char *)d_total.p + 4, 4,
@@ -1399,19 +1546,41 @@ struct AggOp : gx_op {
                 AP.func[k] = aggs[a].func;
                 AP.val_off[k] = val_off[a];
                 AP.seen_off[k] = seen_off[a];
+                AP.dec_scale[k] = dec_scale[a];
                 if (aggs[a].input_col >= 0) AP.input[k] = st.views[aggs[a].input_col];
                 else std::memset(&AP.input[k], 0, sizeof(DevColView));
                 k++;
             }
             AP.n_aggs = k;
+            AP.dec_err = (uint32_t *)d_decerr.p;
+            auto k_accum = has_dec ? k_agg_accumulate_dec : k_agg_accumulate;
             if (k > 0 || !has_distinct)
-                hipLaunchKernelGGL(k_agg_accumulate, dim3(gx_grid(n)), dim3(256),
-                                   0, stream, AP);
+                hipLaunchKernelGGL(k_accum, dim3(gx_grid(n)), dim3(256), 0,
+                                   stream, AP);
         }
         for (auto &ds : dsets)
             if (distinct_pass(ds, st, n, no_group_by)) return -1;
         HIP_OK(hipEventRecord(ev1, stream));
+        uint32_t dec_fence = 0;
+        if (has_dec_input)
+            HIP_OK(hipMemcpyAsync(&dec_fence, d_decerr.p, 4,
+                                  hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
+        if (dec_fence) {
+            /* sticky on the device as well: the op is poisoned, like after
+             * any failed consume */
+            std::string what;
+            if (dec_fence & GX_DEC_FENCE_FRAC)
+                what += " [fractions fence: a value has more fraction "
+                        "digits than the aggregate's scale]";
+            if (dec_fence & GX_DEC_FENCE_WORDS)
+                what += " [words fence: a record has more than 9 base-1e9 "
+                        "words]";
+            if (dec_fence & GX_DEC_FENCE_MAG)
+                what += " [magnitude fence: |value x 10^scale| >= 10^29]";
+            gx_set_err("SUM_DEC/AVG_DEC DECIMAL input rejected:" + what);
+            return -1;
+        }
         {
             float ms = 0;
             HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
@@ -1442,7 +1611,8 @@ struct AggOp : gx_op {
         for (auto &sp : aggs) {
             bool f64 = sp.func == GX_AGG_SUM_F64 || sp.func == GX_AGG_MIN_F64 ||
                        sp.func == GX_AGG_MAX_F64 || sp.func == GX_AGG_AVG_F64;
-            otypes.push_back(f64 ? GX_F64 : GX_I64);
+            otypes.push_back(agg_func_is_dec(sp.func) ? GX_DECIMAL
+                             : f64 ? GX_F64 : GX_I64);
         }
         auto h = alloc_result_cols(otypes, ng, device, stream);
         if (!h) return -1;
@@ -1490,6 +1660,7 @@ struct AggOp : gx_op {
                 EP.func[a] = aggs[a].func;
                 EP.val_off[a] = val_off[a];
                 EP.seen_off[a] = seen_off[a];
+                EP.dec_scale[a] = dec_scale[a];
                 EP.out_vals[a] = h->bufs[col * 2].p;
                 EP.out_nulls[a] = (uint8_t *)h->bufs[col * 2 + 1].p;
                 col++;
@@ -1536,6 +1707,44 @@ gx_op *gxop_agg_create(const gx_agg_cfg *cfg) {
                                ": func " + std::to_string(f) +
                                " does not take input type " +
                                std::to_string(t));
+                    return nullptr;
+                }
+                continue;
+            }
+            if (agg_func_is_dec(f & 0xFFFF)) {
+                /* the input's decimal scale rides in the upper 16 bits */
+                const int32_t base = f & 0xFFFF;
+                const uint32_t scale = (uint32_t)f >> 16;
+                const int32_t col = cfg->aggs[i].input_col;
+                const char *name = base == GX_AGG_SUM_DEC ? "SUM_DEC"
+                                                          : "AVG_DEC";
+                if (scale > 9u) {
+                    gx_set_err(std::string(name) + " agg " +
+                               std::to_string(i) + ": scale " +
+                               std::to_string(scale) +
+                               " not supported (0..9, one fraction word)");
+                    return nullptr;
+                }
+                if (base == GX_AGG_AVG_DEC && scale > 4u) {
+                    gx_set_err("AVG_DEC agg " + std::to_string(i) +
+                               ": scale " + std::to_string(scale) +
+                               " not supported (the result has scale 4: "
+                               "input scale 0..4)");
+                    return nullptr;
+                }
+                if (col < 0 || col >= cfg->n_input_cols) {
+                    gx_set_err(std::string(name) + " agg " +
+                               std::to_string(i) + ": input_col " +
+                               std::to_string(col) + " out of range");
+                    return nullptr;
+                }
+                const int32_t t = cfg->input_types[col];
+                if (t != GX_I64 && t != GX_I32 && t != GX_DECIMAL) {
+                    gx_set_err(std::string(name) + " agg " +
+                               std::to_string(i) +
+                               ": does not take input type " +
+                               std::to_string(t) +
+                               " (I64, I32 or DECIMAL)");
                     return nullptr;
                 }
                 continue;

@@ -914,6 +914,11 @@ gx_op *gxop_fwindow_create(const gx_fwindow_cfg *cfg) {
                        "(not supported in frame-window)");
             return nullptr;
         }
+        if (gx_agg_is_dec(f.func)) {
+            gx_set_err("SUM_DEC/AVG_DEC are gxop_agg only "
+                       "(not supported in frame-window)");
+            return nullptr;
+        }
         if (f.func == GX_AGG_RANK || f.func == GX_AGG_DENSE_RANK) {
             gx_set_err("RANK/DENSE_RANK are window-only");
             return nullptr;

@@ -776,6 +776,13 @@ gx_op *gxop_groupjoin_create(const gx_groupjoin_cfg *cfg) {
             }
     if (cfg)
         for (int32_t i = 0; i < cfg->n_aggs; i++)
+            if (gx_agg_is_dec(cfg->aggs[i].func)) {
+                gx_set_err("SUM_DEC/AVG_DEC are gxop_agg only "
+                           "(not supported in group-join)");
+                return nullptr;
+            }
+    if (cfg)
+        for (int32_t i = 0; i < cfg->n_aggs; i++)
             if (cfg->aggs[i].func == GX_AGG_RANK ||
                 cfg->aggs[i].func == GX_AGG_DENSE_RANK) {
                 gx_set_err("RANK/DENSE_RANK are window-only");

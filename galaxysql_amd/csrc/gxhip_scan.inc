@@ -174,6 +174,7 @@ __device__ static inline AggVal proj_value(int32_t op, const DevColView &a,
                                            const DevColView &dd, int64_t src) {
     AggVal v;
     v.bits = 0;
+    v.hi = 0; /* SUM_DEC / AVG_DEC never take a projection's value */
     v.type = GX_I64;
     switch (op) {
     case GX_PROJ_COPY:
@@ -542,6 +543,7 @@ struct AccumFlush {
                     if (a >= G.n_aggs || !active) continue;
                     AggVal v;
                     v.bits = 0;
+                    v.hi = 0;
                     v.type = GX_I64;
                     v.isnull = false;
                     if (G.func[a] != GX_AGG_COUNT_ROW)
@@ -569,6 +571,7 @@ struct AccumFlush {
             for (int a = 0; a < G.n_aggs; a++) {
                 AggVal v;
                 v.bits = 0;
+                v.hi = 0;
                 v.type = GX_I64;
                 v.isnull = false;
                 if (G.func[a] != GX_AGG_COUNT_ROW)

@@ -650,6 +650,11 @@ gx_op *gxop_window_create(const gx_window_cfg *cfg) {
                        "(not supported in window)");
             return nullptr;
         }
+        if (gx_agg_is_dec(f)) {
+            gx_set_err("SUM_DEC/AVG_DEC are gxop_agg only "
+                       "(not supported in window)");
+            return nullptr;
+        }
         /* running window: accumulators + rank family + null-init Sum;
          * navigation/distribution funcs are frame-window only */
         if ((f < GX_AGG_COUNT_ROW || f > GX_AGG_DENSE_RANK) &&

@@ -132,7 +132,17 @@ def final_agg_specs(n_group_cols, aggs):
                 "AVG must be planned as partial SUM+COUNT around an "
                 "exchange (the reference planner does the same split); "
                 "it never crosses a shuffle as AVG")
-        if func in (abi.COUNT_ROW, abi.COUNT_COL):
+        if abi.base_func(func) == abi.AVG_DEC:
+            raise ValueError(
+                "AVG_DEC must be planned as partial SUM_DEC+COUNT around an "
+                "exchange (the reference planner does the same split); "
+                "it never crosses a shuffle as AVG")
+        if abi.base_func(func) == abi.SUM_DEC:
+            # the partial column is a DECIMAL at the same scale; wide
+            # partial sums (past 18 digits) re-aggregate exactly
+            finals.append((func, col))
+            out_types.append(4)  # DECIMAL
+        elif func in (abi.COUNT_ROW, abi.COUNT_COL):
             finals.append((abi.SUM_I64, col))
             out_types.append(0)  # I64
         elif func in (abi.SUM_I64, abi.SUM_I64N, abi.MIN_I64, abi.MAX_I64,

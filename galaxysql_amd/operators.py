@@ -187,7 +187,11 @@ class ParallelHashJoinExec:
 class HashAggExec:
     def __init__(self, lib, group_cols, aggs, input_types,
                  expected_groups=0, device=-1, stream=0):
-        """aggs: list of (abi.COUNT_ROW.., input_col_or_-1)."""
+        """aggs: list of (abi.COUNT_ROW.., input_col_or_-1). The exact DECIMAL
+        sums carry their input's scale in the func: (abi.sum_dec(s), col) /
+        (abi.avg_dec(s), col) over an I64/I32 column of integers scaled by
+        10^s or a DECIMAL column; their result column is DECIMAL (decode
+        with chunk.dec40_decode_wide)."""
         self._lib = lib
         self._keep = []
         gc = (C.c_int32 * max(1, len(group_cols)))(*(group_cols or [0]))

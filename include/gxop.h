@@ -301,12 +301,66 @@ typedef enum gx_agg_func {
     GX_AGG_SUM_I64N_DISTINCT = 25, /* Sum / Long2DecimalSum family: BIGINT,
                                       NULL when no non-null input */
     GX_AGG_SUM_F64_DISTINCT  = 26, /* Double2DoubleSum: DOUBLE, init NULL */
-    GX_AGG_AVG_F64_DISTINCT  = 27  /* Avg over doubles: state {sum, count}
+    GX_AGG_AVG_F64_DISTINCT  = 27, /* Avg over doubles: state {sum, count}
                                       over the distinct values, init NULL */
+    /* Exact DECIMAL SUM / AVG — what AggregateUtils maps SQL SUM / AVG to
+     * for integer and DECIMAL arguments (AggregateUtils.java:175-197:
+     * Long2DecimalSum, Int2DecimalSum, Decimal2DecimalSum, *2DecimalAvg).
+     * None of them wraps: LittleNum2DecimalSum.java:56-68 spills into a
+     * Decimal on overflow, Decimal2DecimalSum accumulates in a DecimalBox
+     * then FastDecimalUtils.add. (SUM_I64 / SUM_I64N keep their Java
+     * wrap-around u64 — right for Long2LongSum0, unchanged.)
+     *  - The func field carries the input's decimal scale s in its upper
+     *    16 bits: pass GX_AGG_WITH_SCALE(GX_AGG_SUM_DEC, s). 0 <= s <= 9
+     *    (one fraction word); AVG_DEC takes s <= 4. Anything else fails at
+     *    create. Every other func has zero upper bits.
+     *  - Input GX_I64 / GX_I32: an integer already scaled by 10^s (s = 0:
+     *    Long2DecimalSum / Int2DecimalSum over BIGINT / INT; s > 0: the
+     *    scaled-int64 decimal form, e.g. the output of REV_SCALED4,
+     *    Q9_AMOUNT4 or DEC_TO_SCALED). Input GX_DECIMAL: 40-B records in
+     *    the general DecimalStructure layout (DecimalTypeBase.java:61-65,
+     *    101-102: roundUp(integers) base-1e9 integer words, most
+     *    significant first, then roundUp(fractions) fraction words, the
+     *    last left-aligned, sign at byte 39), each brought to scale s on
+     *    the device. A value with fractions > s, with more than 9 words,
+     *    or with |value x 10^s| >= 10^29 sets a sticky device flag; the
+     *    consume that carried it fails and gx_last_error() names the fence
+     *    (the scan's wide-DECIMAL fence mechanism). The op is then poisoned
+     *    like after any failed consume: close it.
+     *  - NULL inputs never accumulate; a group without a non-NULL input
+     *    emits NULL, and so does a global aggregate over empty input.
+     *  - Output: one GX_DECIMAL column. |sum| is written as base-1e9
+     *    integer words, most significant first (at least one), then one
+     *    fraction word frac x 10^(9-s); integers = 9 x integer words,
+     *    fractions = derivedFractions = s, isNeg = 0 for zero — the layout
+     *    DecimalBox.doAddToSum1/2 writes for the first two widths, wider
+     *    sums continue it. AVG_DEC emits round_half_up(sum / count, 4) at
+     *    scale 4, rounding the magnitude (SpecificType2DecimalAvg
+     *    .writeResultTo:93-114, DEFAULT_DIV_PRECISION_INCREMENT = 4).
+     *  - Exactness: the state is a two's-complement 128-bit integer plus a
+     *    seen flag (SUM) or a count (AVG); the sum is exact while
+     *    sum(|v|) < 2^127. Integer columns cannot leave that bound within
+     *    the table's 2^32-row limit; DECIMAL inputs, fenced at 10^29, leave
+     *    it only past 2^30 values. AVG additionally needs
+     *    |sum| x 10^(4-s) < 2^128. Overflow beyond these bounds is NOT
+     *    detected.
+     *  - gxop_agg_create ONLY (grouped and global): the group-join, window
+     *    and frame-window creates reject these (their emit kernels write
+     *    8-B values). No DISTINCT variants, no per-aggregator FILTER,
+     *    scales above 9 and precision beyond 38 digits stay on the CPU (the
+     *    reference allows 65/30).
+     *  - Two-phase plans: a partial SUM_DEC(s) column re-aggregates as
+     *    SUM_DEC(s) over the DECIMAL partial column; AVG_DEC is planned as
+     *    SUM_DEC + COUNT. */
+    GX_AGG_SUM_DEC = 28,
+    GX_AGG_AVG_DEC = 29
 } gx_agg_func;
 
+/* SUM_DEC / AVG_DEC: the input's decimal scale rides in func's upper half */
+#define GX_AGG_WITH_SCALE(func, s) ((func) | ((s) << 16))
+
 typedef struct gx_agg_spec {
-    int32_t func;        /* gx_agg_func */
+    int32_t func;        /* gx_agg_func; SUM_DEC/AVG_DEC: GX_AGG_WITH_SCALE */
     int32_t input_col;   /* column in the input chunk; -1 for COUNT_ROW */
 } gx_agg_spec;
 

@@ -517,6 +517,71 @@ static void t_agg_empty_global(int device) {
     std::printf("  agg empty-global: one row, COUNT=0, SUM NULL\n");
 }
 
+/* exact DECIMAL SUM (GX_AGG_SUM_DEC, 128-bit state): 4096 x INT64_MAX into
+ * one group gives 4096 x (2^63-1) = 2^75 - 4096 = 37778 931862957 161705472,
+ * i.e. three base-1e9 integer words, a zero fraction word, integers = 27,
+ * scale 0, not negative; its companion group holds only NULLs and emits
+ * NULL. Skipped on the CPU oracle, which does not have the func. */
+static void t_decsum(int device) {
+    if (api.abi_version() == 0) {
+        std::printf("  decsum: not in this library, skipped\n");
+        return;
+    }
+    const int N = 4096, NN = 16;
+    std::vector<int64_t> gk(N + NN), v(N + NN);
+    std::vector<uint8_t> nulls(N + NN, 0);
+    for (int i = 0; i < N + NN; i++) {
+        gk[i] = i < N ? 7 : 8;
+        v[i] = INT64_MAX;
+        nulls[i] = i < N ? 0 : 1;
+    }
+    int32_t gcols[1] = {0};
+    gx_agg_spec specs[1] = {{GX_AGG_WITH_SCALE(GX_AGG_SUM_DEC, 0), 1}};
+    int32_t itypes[2] = {GX_I64, GX_I64};
+    gx_agg_cfg cfg{};
+    cfg.n_group_cols = 1; cfg.group_cols = gcols;
+    cfg.n_aggs = 1; cfg.aggs = specs;
+    cfg.n_input_cols = 2; cfg.input_types = itypes;
+    cfg.device = device;
+    gx_op *op = api.agg_create(&cfg);
+    CHECK(op, "decsum agg_create");
+    if (!op) return;
+    gx_block bb[2] = {mk_i64(gk.data()), mk_i64(v.data(), nulls.data())};
+    gx_chunk c{N + NN, 2, bb};
+    CHECK(api.agg_consume(op, &c) == 0, "decsum consume");
+    CHECK(api.agg_build(op) == 0, "decsum build");
+    uint8_t expect[40] = {0};
+    const int32_t words[3] = {37778, 931862957, 161705472};
+    std::memcpy(expect, words, sizeof(words));
+    expect[36] = 27;
+    int seen_sum = 0, seen_null = 0;
+    for (;;) {
+        gx_result *res = nullptr;
+        CHECK(api.agg_next(op, &res) == 0, "decsum next");
+        if (!res) break;
+        api.result_to_host(res);
+        CHECK(res->chunk.blocks[1].type == GX_DECIMAL, "decsum out type");
+        for (int r = 0; r < res->chunk.n_rows; r++) {
+            const uint8_t *rec =
+                (const uint8_t *)res->chunk.blocks[1].values + (size_t)r * 40;
+            if (cell_i64(res, 0, r) == 7) {
+                CHECK(!cell_null(res, 1, r) &&
+                          std::memcmp(rec, expect, 40) == 0,
+                      "decsum: 4096 x INT64_MAX record mismatch");
+                seen_sum++;
+            } else {
+                CHECK(cell_null(res, 1, r), "decsum: NULL group not NULL");
+                seen_null++;
+            }
+        }
+        api.result_release(res);
+    }
+    CHECK(seen_sum == 1 && seen_null == 1, "decsum groups %d/%d", seen_sum,
+          seen_null);
+    api.agg_close(op);
+    std::printf("  decsum: 4096 x INT64_MAX exact, NULL group NULL\n");
+}
+
 /* partition: row conservation + consume/consume_concat agreement. */
 static void t_part(int device) {
     const int N = 50000, PARTS = 8;
@@ -1159,6 +1224,7 @@ int main(int argc, char **argv) {
         t_join_left(device);
         t_agg(device);
         t_agg_empty_global(device);
+        t_decsum(device);
         t_part(device);
         t_scan(device);
         t_groupjoin(device);
