@@ -425,6 +425,15 @@ class GxLib:
                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             L.gxop_groupjoin_get_stats.argtypes = [C.c_void_p,
                                                    C.POINTER(GxJoinStats)]
+        # producer join's matches straight into a group-join's build: HIP
+        # library only as well
+        self.has_groupjoin_build_probe_scan = hasattr(
+            L, "gxop_groupjoin_build_probe_scan")
+        if self.has_groupjoin_build_probe_scan:
+            L.gxop_groupjoin_build_probe_scan.argtypes = [
+                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GxChunk),
+                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            L.gxop_groupjoin_build_was_fused.argtypes = [C.c_void_p]
         # sort / top-N (ORDER BY ... LIMIT): HIP library only as well
         self.has_sort = hasattr(L, "gxop_sort_create")
         if self.has_sort:

@@ -417,6 +417,48 @@ __device__ static inline uint32_t join_row_bucket(const JoinInsertParams &P,
     return (uint32_t)gx_mix(h) & P.mask;
 }
 
+/* Insert one build row: rank atomic on the bucket's count word, slot store
+ * for ranks 0..3, bloom bits, wave-aggregated spill append for later ranks.
+ * Called by every lane of the wave (the append ballots across it); a lane
+ * that is not `live` inserts nothing. Shared by k_join_insert and the
+ * group-join's k_join_insert_proj (gxhip_scan.inc). */
+__device__ static inline void join_insert_row(const JoinInsertParams &P,
+                                              bool live, int64_t key,
+                                              uint32_t b, int64_t i,
+                                              int lane) {
+    uint32_t rank = 0;
+    if (live) {
+        JoinEntry *bucket = P.table + (uint64_t)b * 4;
+        rank = atomicAdd(&bucket[0].pad, 1u);
+        if (rank < 4) {
+            bucket[rank].key = key;   /* 12-B store; pad untouched */
+            bucket[rank].pos = (uint32_t)i;
+        }
+        if (P.bloom) {
+            uint64_t x = bloom_mix(key);
+            atomicOr(&P.bloom[bloom_word(x, P.bloom_mask)],
+                     (unsigned long long)bloom_bits(x));
+        }
+    }
+    /* wave-aggregated append: one counter atomic per wave (a per-lane
+     * add on one word serializes at ~88/us) */
+    bool spilled = live && rank >= 4;
+    unsigned long long m = __ballot(spilled);
+    if (m) {
+        int leader = __ffsll((long long)m) - 1;
+        uint32_t base = 0;
+        if (lane == leader)
+            base = atomicAdd(P.spill_count, (uint32_t)__popcll(m));
+        base = (uint32_t)__shfl((int)base, leader, 64);
+        if (spilled) {
+            JoinSpill s;
+            s.row = (uint32_t)i;
+            s.rank = rank;
+            P.spill[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = s;
+        }
+    }
+}
+
 __global__ void k_join_insert(JoinInsertParams P) {
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -429,39 +471,10 @@ __global__ void k_join_insert(JoinInsertParams P) {
          * (ExecUtils.buildOneChunk:933-941) */
         if (live)
             live = P.fast_i64 ? !col_is_null(P.key0, i) : !P.keynull[i];
-        uint32_t rank = 0;
-        if (live) {
-            int64_t key;
-            uint32_t b = join_row_bucket(P, i, key);
-            JoinEntry *bucket = P.table + (uint64_t)b * 4;
-            rank = atomicAdd(&bucket[0].pad, 1u);
-            if (rank < 4) {
-                bucket[rank].key = key;   /* 12-B store; pad untouched */
-                bucket[rank].pos = (uint32_t)i;
-            }
-            if (P.bloom) {
-                uint64_t x = bloom_mix(key);
-                atomicOr(&P.bloom[bloom_word(x, P.bloom_mask)],
-                         (unsigned long long)bloom_bits(x));
-            }
-        }
-        /* wave-aggregated append: one counter atomic per wave (a per-lane
-         * add on one word serializes at ~88/us) */
-        bool spilled = live && rank >= 4;
-        unsigned long long m = __ballot(spilled);
-        if (m) {
-            int leader = __ffsll((long long)m) - 1;
-            uint32_t base = 0;
-            if (lane == leader)
-                base = atomicAdd(P.spill_count, (uint32_t)__popcll(m));
-            base = (uint32_t)__shfl((int)base, leader, 64);
-            if (spilled) {
-                JoinSpill s;
-                s.row = (uint32_t)i;
-                s.rank = rank;
-                P.spill[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = s;
-            }
-        }
+        int64_t key = 0;
+        uint32_t b = 0;
+        if (live) b = join_row_bucket(P, i, key);
+        join_insert_row(P, live, key, b, i, lane);
     }
 }
 
@@ -1421,6 +1434,19 @@ struct JoinOp : gx_op {
     }
 
     int do_build() {
+        return do_build_with([this](const JoinInsertParams &IP) {
+            hipLaunchKernelGGL(k_join_insert, dim3(gx_grid(IP.n)), dim3(256),
+                               0, stream, IP);
+        });
+    }
+
+    /* The build, with the inline-bucket insert kernel launched by
+     * `launch_insert(IP)`: k_join_insert over the store's key column
+     * (do_build), or a kernel that fills the store's rows itself and inserts
+     * each key from a register (gxop_groupjoin_build_probe_scan; the store
+     * is then sized, n_rows set, before this runs). */
+    template <class LaunchInsert>
+    int do_build_with(LaunchInsert &&launch_insert) {
         /* first-come barrier contract (Synchronizer.buildCount): the first
          * caller builds, later callers no-op */
         if (built) return 0;
@@ -1546,8 +1572,7 @@ struct JoinOp : gx_op {
             IP.spill_count = (uint32_t *)d_counts.p;
             IP.bloom = use_bloom ? (unsigned long long *)d_bloom.p : nullptr;
             IP.bloom_mask = bloom_mask;
-            hipLaunchKernelGGL(k_join_insert, dim3(gx_grid(n)), dim3(256), 0,
-                               stream, IP);
+            launch_insert(IP);
             uint32_t n_spill = 0;
             HIP_OK(hipMemcpyAsync(&n_spill, d_counts.p, 4,
                                   hipMemcpyDeviceToHost, stream));

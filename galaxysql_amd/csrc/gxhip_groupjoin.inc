@@ -394,6 +394,8 @@ struct GroupJoinOp : gx_op {
      * kept (LEFT, the CSR and wide modes, no COUNT(*)). Set at do_build,
      * before the first probe, so every probe kernel and the emission agree. */
     int32_t count_off = -1;
+    /* the build came through gxop_groupjoin_build_probe_scan's fast path */
+    bool build_fused = false;
 
     GroupJoinOp(const gx_groupjoin_cfg *c)
         : gx_op(OP_GROUPJOIN, c->device, c->stream), cfg(*c) {
@@ -474,6 +476,16 @@ struct GroupJoinOp : gx_op {
     int consume(const gx_chunk *ch) { return jop->consume(ch); }
 
     int do_build() {
+        return do_build_with([this](const JoinInsertParams &IP) {
+            hipLaunchKernelGGL(k_join_insert, dim3(gx_grid(IP.n)), dim3(256),
+                               0, stream, IP);
+        });
+    }
+
+    /* do_build with the inner join's insert kernel launched by the caller
+     * (JoinOp::do_build_with) */
+    template <class LaunchInsert>
+    int do_build_with(LaunchInsert &&launch_insert) {
         inline_tab = inline_ok && jop->build.n_rows > 0 &&
                      !jop->build.cols[jop->build_key_cols[0]].has_nulls;
         jop->null_safe_keys = !inline_tab;
@@ -481,7 +493,7 @@ struct GroupJoinOp : gx_op {
         if (inline_tab && cfg.join_type == GX_JOIN_INNER)
             for (size_t a = 0; a < aggs.size() && count_off < 0; a++)
                 if (aggs[a].func == GX_AGG_COUNT_ROW) count_off = val_off[a];
-        if (jop->do_build()) return -1;
+        if (jop->do_build_with(launch_insert)) return -1;
         const int64_t n = jop->build.n_rows;
         if (d_meta.grow(16, stream)) return -1;
         HIP_OK(hipMemsetAsync(d_meta.p, 0, 16, stream));

@@ -624,6 +624,64 @@ __global__ void k_gather_proj(ProjGatherParams G) {
     }
 }
 
+/* ---- gather + insert (gxop_groupjoin_build_probe_scan fast path) -------
+ * k_gather_proj and k_join_insert in one pass over the fused probe's pair
+ * list: pair i evaluates every consumed column (register-sized: proj_value)
+ * at its raw row / build position, all loads issued before anything else,
+ * writes the values to row i of the group-join's build store (adjacent
+ * lanes, adjacent rows) and inserts (key, i) from the register. The random
+ * loads then ride beside the insert's atomics, which set the pace. The
+ * column loops are unrolled over GX_JIP_MAX_COLS so the values stay in
+ * registers; wider schemas take the composed path. */
+#define GX_JIP_MAX_COLS 8
+
+__global__ void __launch_bounds__(256)
+k_join_insert_proj(JoinInsertParams P, ProjGatherParams G, int32_t key_col) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    /* wave-uniform trip count: the spill append ballots across the wave */
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;;
+         i += stride) {
+        const bool live = i < P.n;
+        if (!__ballot(live)) break;
+        unsigned long long val[GX_JIP_MAX_COLS];
+        uint32_t nullm = 0;
+        int64_t key = 0;
+        if (live) {
+            const int64_t pi = G.pidx[i];
+            const int64_t bi = G.bidx[i];
+#pragma unroll
+            for (int c = 0; c < GX_JIP_MAX_COLS; c++) {
+                val[c] = 0;
+                if (c < G.n_cols) {
+                    const AggVal v = proj_value(G.op[c], G.a[c], G.b[c],
+                                                G.c[c], G.d[c],
+                                                G.side[c] ? bi : pi);
+                    val[c] = v.bits;
+                    if (v.isnull) nullm |= 1u << c;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < GX_JIP_MAX_COLS; c++) {
+                if (c < G.n_cols) {
+                    if (G.out_nulls[c])
+                        G.out_nulls[c][i] = (uint8_t)((nullm >> c) & 1u);
+                    /* as proj_store: an I32 COPY stores 4 B, all else 8 B */
+                    if (G.op[c] == GX_PROJ_COPY && G.a[c].type == GX_I32)
+                        ((int32_t *)G.out_vals[c])[i] = (int32_t)val[c];
+                    else
+                        ((unsigned long long *)G.out_vals[c])[i] = val[c];
+                    if (c == key_col) key = (int64_t)val[c];
+                }
+            }
+        }
+        /* the key column is null-free (a fast-path condition): every live
+         * row is inserted */
+        const uint32_t b = (uint32_t)gx_mix(gx_hash_i64(key)) & P.mask;
+        join_insert_row(P, live, key, b, i, lane);
+    }
+}
+
 __global__ void k_scan(ScanParams P) {
     /* per-wave LDS staging of surviving row indices, then each flush
      * writes the projected columns coalesced (same batching rationale as
@@ -848,12 +906,14 @@ bool probe_scan_fast_ok(const JoinOp *j, const ScanOp *s,
     return true;
 }
 
-int probe_scan_fused(JoinOp *j, ScanOp *s, const gx_chunk *raw,
-                     gx_result **out, int64_t *n_kept) {
-    if (ensure_device(j->device)) return -1;
+/* Stage 1 of the fused probe: k_probe_scan over the staged raw chunk. On
+ * return the (raw row, build position) pairs of the *n_out matches sit in
+ * j->d_pidx / j->d_bpos (until the op's next probe), *n_kept holds the rows
+ * that passed the predicates, the join's stats are advanced and the stream
+ * is drained. */
+int probe_scan_pairs(JoinOp *j, ScanOp *s, const StagedChunk &st,
+                     int64_t *n_out, int64_t *n_kept) {
     hipStream_t stream = j->stream;
-    StagedChunk st;
-    if (st.stage(raw, stream)) return -1; /* device-resident: zero copy */
     const int64_t n = st.n_rows;
     ScanPreds S;
     if (s->fill_preds(S, st)) return -1;
@@ -907,60 +967,92 @@ int probe_scan_fused(JoinOp *j, ScanOp *s, const gx_chunk *raw,
         }
         if (meta[0] > cap) { cap = meta[0]; continue; } /* exact-size retry */
 
-        const int64_t n_out = meta[0];
+        *n_out = meta[0];
         j->probe_rows_total += meta[2];
-        j->matches_total += n_out;
+        j->matches_total += meta[0];
         *n_kept = meta[2];
-        std::vector<JoinOp::OutSpec> specs = j->projected_specs();
-        std::vector<int32_t> otypes;
-        std::vector<uint8_t> null_free; /* as in the scan and the join */
-        for (auto &sp : specs) {
-            otypes.push_back(sp.type);
-            null_free.push_back(sp.outer
-                ? s->proj_null_free((size_t)sp.src, st)
-                : !j->build.view(sp.src).has_nulls);
-        }
-        auto h = alloc_result_cols(otypes, n_out, j->device, stream,
-                                   &null_free);
-        if (!h) return -1;
-        if (n_out > 0) {
-            ProjGatherParams G;
-            std::memset(&G, 0, sizeof(G));
-            G.pidx = (const uint32_t *)j->d_pidx.p;
-            G.bidx = (const uint32_t *)j->d_bpos.p;
-            G.n = n_out;
-            G.n_cols = (int32_t)specs.size();
-            for (size_t c = 0; c < specs.size(); c++) {
-                G.out_vals[c] = h->bufs[c * 2].p;
-                G.out_nulls[c] = (uint8_t *)h->bufs[c * 2 + 1].p;
-                if (!specs[c].outer) { /* build side: plain gather */
-                    G.side[c] = 1;
-                    G.op[c] = GX_PROJ_COPY;
-                    G.a[c] = j->build.view(specs[c].src);
-                    continue;
-                }
-                const gx_proj &pr = s->projs[(size_t)specs[c].src];
-                G.side[c] = 0;
-                G.op[c] = pr.op;
-                G.a[c] = st.views[pr.a];
-                if (pr.op == GX_PROJ_SCALED_TO_DEC)
-                    G.scale[c] = pr.c;   /* c = scale, not a col */
-                else if (pr.op != GX_PROJ_COPY)
-                    G.b[c] = st.views[pr.b];
-                if (pr.op == GX_PROJ_Q9_AMOUNT4) {
-                    G.c[c] = st.views[pr.c];
-                    G.d[c] = st.views[pr.d];
-                }
-            }
-            hipLaunchKernelGGL(k_gather_proj, dim3(gx_grid(n_out)), dim3(256),
-                               0, stream, G);
-            /* the pair lists are reused by the next probe: drain first */
-            HIP_OK(hipStreamSynchronize(stream));
-        }
-        give_result(std::move(h), out);
         return 0;
     }
-    return -1; /* pair list still short after 4 resizes */
+    gx_set_err("probe_scan: pair list still short after 4 resizes");
+    return -1;
+}
+
+/* the source half of ProjGatherParams for the fused probe's pair list: per
+ * output column of `specs`, the scan projection it evaluates at the raw row
+ * or the build column it gathers (G zeroed by the caller; out_vals /
+ * out_nulls are the caller's) */
+void fill_proj_gather(ProjGatherParams &G, const JoinOp *j, const ScanOp *s,
+                      const StagedChunk &st,
+                      const std::vector<JoinOp::OutSpec> &specs,
+                      int64_t n_out) {
+    G.pidx = (const uint32_t *)j->d_pidx.p;
+    G.bidx = (const uint32_t *)j->d_bpos.p;
+    G.n = n_out;
+    G.n_cols = (int32_t)specs.size();
+    for (size_t c = 0; c < specs.size(); c++) {
+        if (!specs[c].outer) { /* build side: plain gather */
+            G.side[c] = 1;
+            G.op[c] = GX_PROJ_COPY;
+            G.a[c] = j->build.view(specs[c].src);
+            continue;
+        }
+        const gx_proj &pr = s->projs[(size_t)specs[c].src];
+        G.side[c] = 0;
+        G.op[c] = pr.op;
+        G.a[c] = st.views[pr.a];
+        if (pr.op == GX_PROJ_SCALED_TO_DEC)
+            G.scale[c] = pr.c;   /* c = scale, not a col */
+        else if (pr.op != GX_PROJ_COPY)
+            G.b[c] = st.views[pr.b];
+        if (pr.op == GX_PROJ_Q9_AMOUNT4) {
+            G.c[c] = st.views[pr.c];
+            G.d[c] = st.views[pr.d];
+        }
+    }
+}
+
+/* is output column `sp` of the fused probe null-free? (as in the scan and
+ * the join) */
+bool probe_scan_col_null_free(const JoinOp *j, const ScanOp *s,
+                              const StagedChunk &st,
+                              const JoinOp::OutSpec &sp) {
+    return sp.outer ? s->proj_null_free((size_t)sp.src, st)
+                    : !j->build.view(sp.src).has_nulls;
+}
+
+int probe_scan_fused(JoinOp *j, ScanOp *s, const gx_chunk *raw,
+                     gx_result **out, int64_t *n_kept) {
+    if (ensure_device(j->device)) return -1;
+    hipStream_t stream = j->stream;
+    StagedChunk st;
+    if (st.stage(raw, stream)) return -1; /* device-resident: zero copy */
+    int64_t n_out = 0;
+    if (probe_scan_pairs(j, s, st, &n_out, n_kept)) return -1;
+
+    std::vector<JoinOp::OutSpec> specs = j->projected_specs();
+    std::vector<int32_t> otypes;
+    std::vector<uint8_t> null_free;
+    for (auto &sp : specs) {
+        otypes.push_back(sp.type);
+        null_free.push_back(probe_scan_col_null_free(j, s, st, sp));
+    }
+    auto h = alloc_result_cols(otypes, n_out, j->device, stream, &null_free);
+    if (!h) return -1;
+    if (n_out > 0) {
+        ProjGatherParams G;
+        std::memset(&G, 0, sizeof(G));
+        fill_proj_gather(G, j, s, st, specs, n_out);
+        for (size_t c = 0; c < specs.size(); c++) {
+            G.out_vals[c] = h->bufs[c * 2].p;
+            G.out_nulls[c] = (uint8_t *)h->bufs[c * 2 + 1].p;
+        }
+        hipLaunchKernelGGL(k_gather_proj, dim3(gx_grid(n_out)), dim3(256),
+                           0, stream, G);
+        /* the pair lists are reused by the next probe: drain first */
+        HIP_OK(hipStreamSynchronize(stream));
+    }
+    give_result(std::move(h), out);
+    return 0;
 }
 
 /* ---- fused scan + group-join probe (gxop_groupjoin_probe_scan) -------- */
@@ -1077,9 +1169,157 @@ int gj_probe_scan_fused(GroupJoinOp *g, ScanOp *s, const gx_chunk *raw,
     return 0;
 }
 
+/* ---- join1's matches straight into the group-join's build
+ *      (gxop_groupjoin_build_probe_scan) -------------------------------- */
+
+/* The fast path's conditions that can be told before the probe (gxop_hip.h):
+ * the producer join's own fused fast path, a group-join that has consumed
+ * nothing and would build the inline-bucket table, a null-free key
+ * projection, register-sized consumed columns only (at most
+ * GX_JIP_MAX_COLS), one device and stream. GX_GJ_BUILD_FUSED=0, read per
+ * call, turns it off. */
+bool gj_build_probe_scan_fast_ok(const GroupJoinOp *g, const JoinOp *j,
+                                 const ScanOp *s, const gx_chunk *raw,
+                                 const StagedChunk &st) {
+    const char *e = getenv("GX_GJ_BUILD_FUSED");
+    if (e && e[0] == '0') return false;
+    if (!probe_scan_fast_ok(j, s, raw)) return false;
+    if (g->built || g->jop->built || g->jop->build.n_rows != 0 ||
+        !g->inline_ok)
+        return false;
+    if (g->device != j->device || g->stream != j->stream) return false;
+    const std::vector<JoinOp::OutSpec> specs = j->projected_specs();
+    if (specs.size() > GX_JIP_MAX_COLS) return false;
+    for (size_t c = 0; c < specs.size(); c++) {
+        const JoinOp::OutSpec &sp = specs[c];
+        if (sp.type != GX_I64 && sp.type != GX_I32 && sp.type != GX_F64)
+            return false;
+        if (sp.outer && s->projs[(size_t)sp.src].op == GX_PROJ_SCALED_TO_DEC)
+            return false;
+    }
+    /* the consumed key column must come out null-free, else do_build
+     * would not choose the inline-bucket table */
+    const int kc = g->jop->build_key_cols[0];
+    return probe_scan_col_null_free(j, s, st, specs[(size_t)kc]);
+}
+
+/* Size the group-join's (empty) build store for exactly n rows whose
+ * column c carries a nulls buffer unless null_free[c]: what appending the
+ * composed sequence's result would leave, before any row is written. */
+int gj_store_size_exact(DevStore &store, int64_t n,
+                        const std::vector<uint8_t> &null_free) {
+    if (store.reserve(n)) return -1;
+    for (size_t c = 0; c < store.cols.size(); c++) {
+        DevColumn &col = store.cols[c];
+        col.has_nulls = !null_free[c];
+        if (col.has_nulls && col.nulls.grow((size_t)n, store.stream))
+            return -1;
+    }
+    store.n_rows = n;
+    return 0;
+}
+
+int gj_build_probe_scan_fused(GroupJoinOp *g, JoinOp *j, ScanOp *s,
+                              const StagedChunk &st, int64_t *n_kept,
+                              int64_t *n_consumed) {
+    hipStream_t stream = j->stream;
+    int64_t n = 0;
+    if (probe_scan_pairs(j, s, st, &n, n_kept)) return -1;
+    *n_consumed = n;
+    /* an empty consumed side builds as an empty consume would */
+    if (n == 0) return g->do_build();
+
+    const std::vector<JoinOp::OutSpec> specs = j->projected_specs();
+    std::vector<uint8_t> null_free;
+    for (auto &sp : specs)
+        null_free.push_back(probe_scan_col_null_free(j, s, st, sp));
+    DevStore &store = g->jop->build;
+    if (gj_store_size_exact(store, n, null_free)) return -1;
+
+    ProjGatherParams G;
+    std::memset(&G, 0, sizeof(G));
+    fill_proj_gather(G, j, s, st, specs, n);
+    for (size_t c = 0; c < specs.size(); c++) {
+        G.out_vals[c] = store.cols[c].values.p;
+        G.out_nulls[c] = store.cols[c].has_nulls
+            ? (uint8_t *)store.cols[c].nulls.p : nullptr;
+    }
+    const int32_t key_col = (int32_t)g->jop->build_key_cols[0];
+    g->build_fused = true;
+    /* sizes and zeroes table, spill list and bloom for n, launches the
+     * insert through the lambda, then the spill passes, records, d_meta */
+    return g->do_build_with([&](const JoinInsertParams &IP) {
+        hipLaunchKernelGGL(k_join_insert_proj, dim3(gx_grid(IP.n)), dim3(256),
+                           0, stream, IP, G, key_col);
+    });
+}
+
 } // namespace
 
 extern "C" {
+
+int gxop_groupjoin_build_probe_scan(gx_op *groupjoin, gx_op *join,
+                                    gx_op *scan, const gx_chunk *raw_chunk,
+                                    int64_t *n_scan_kept,
+                                    int64_t *n_consumed) {
+    if (!groupjoin || groupjoin->kind != OP_GROUPJOIN) { gx_set_err("not a groupjoin op"); return -1; }
+    if (!join || join->kind != OP_JOIN) { gx_set_err("not a join op"); return -1; }
+    if (!scan || scan->kind != OP_SCAN) { gx_set_err("not a scan op"); return -1; }
+    if (!raw_chunk) { gx_set_err("groupjoin_build_probe_scan: null argument"); return -1; }
+    GroupJoinOp *g = static_cast<GroupJoinOp *>(groupjoin);
+    ScanOp *s = static_cast<ScanOp *>(scan);
+    JoinOp *j = join->variant == 0 ? static_cast<JoinOp *>(join) : nullptr;
+    int64_t kept = 0, consumed = 0;
+    {
+        std::unique_lock<std::mutex> lj(join->mu, std::defer_lock);
+        std::unique_lock<std::mutex> lg(groupjoin->mu, std::defer_lock);
+        std::lock(lj, lg);
+        if (g->built) { gx_set_err("groupjoin_build_probe_scan: already built"); return -1; }
+        /* the fast path checks nothing the composed sequence would
+         * reject: types and build state are tested the same way first */
+        const bool shape_ok = j && j->built &&
+            (j->cfg.build_outer ? j->inner_types : j->outer_types) ==
+                s->out_types &&
+            j->output_types() == g->build_types &&
+            join->device == scan->device && join->stream == scan->stream;
+        if (shape_ok) {
+            if (ensure_device(j->device)) return -1;
+            StagedChunk st; /* device-resident on the fast path: zero copy */
+            bool fast = true;
+            for (int32_t b = 0; b < raw_chunk->n_blocks && fast; b++)
+                fast = raw_chunk->blocks[b].mem == GX_MEM_DEVICE;
+            if (fast && st.stage(raw_chunk, j->stream)) return -1;
+            if (fast && gj_build_probe_scan_fast_ok(g, j, s, raw_chunk, st)) {
+                int rc = gj_build_probe_scan_fused(g, j, s, st, &kept,
+                                                   &consumed);
+                if (rc) return rc;
+                if (n_scan_kept) *n_scan_kept = kept;
+                if (n_consumed) *n_consumed = consumed;
+                return 0;
+            }
+        }
+    }
+    /* composed sequence, each step under its own op's lock */
+    gx_result *t = nullptr;
+    int rc = gxop_join_probe_scan(join, scan, raw_chunk, &t, &kept);
+    if (rc) return rc;
+    if (t) {
+        consumed = t->chunk.n_rows;
+        rc = gxop_groupjoin_consume(groupjoin, &t->chunk);
+        gxop_result_release(t);
+        if (rc) return rc;
+    }
+    rc = gxop_groupjoin_build(groupjoin);
+    if (rc) return rc;
+    if (n_scan_kept) *n_scan_kept = kept;
+    if (n_consumed) *n_consumed = consumed;
+    return 0;
+}
+
+int gxop_groupjoin_build_was_fused(gx_op *groupjoin) {
+    if (!groupjoin || groupjoin->kind != OP_GROUPJOIN) { gx_set_err("not a groupjoin op"); return -1; }
+    return static_cast<GroupJoinOp *>(groupjoin)->build_fused ? 1 : 0;
+}
 
 int gxop_groupjoin_probe_scan(gx_op *groupjoin, gx_op *scan,
                               const gx_chunk *raw_chunk,

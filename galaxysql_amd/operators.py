@@ -411,6 +411,23 @@ class HashGroupJoinExec:
         self._lib.check(self._lib.lib.gxop_groupjoin_build(self._op),
                         "groupjoin_build")
 
+    def build_probe_scan(self, join, scan, chunk_ref):
+        """Consume `join`'s fused probe-scan of the raw chunk (a byref'd
+        GxChunk) and build (gxop_groupjoin_build_probe_scan): the consumed
+        side is never materialized as a result. Returns (rows that passed
+        the scan, rows consumed). Only on a library with
+        has_groupjoin_build_probe_scan."""
+        kept = C.c_int64(0)
+        consumed = C.c_int64(0)
+        self._lib.check(self._lib.lib.gxop_groupjoin_build_probe_scan(
+            self._op, join._op, scan._op, chunk_ref, C.byref(kept),
+            C.byref(consumed)), "groupjoin_build_probe_scan")
+        return kept.value, consumed.value
+
+    def build_was_fused(self):
+        """Did build_probe_scan take the one-kernel fast path?"""
+        return self._lib.lib.gxop_groupjoin_build_was_fused(self._op) == 1
+
     def probe_chunk(self, chunk: Chunk):
         ka = []
         gc = self._lib.to_gx_chunk(chunk, ka)

@@ -115,7 +115,7 @@ def result_to_tensors(lib, res, types, device_t):
 
 
 def _q3_groupjoin(lib, device, r1, n_orders_kept, lineitem, to_host,
-                  keep_results):
+                  keep_results, producer=None):
     """join2 + GROUP BY of Q3 as ONE group-join, probed straight from the
     unscanned lineitem (gxop_groupjoin_probe_scan).
 
@@ -130,7 +130,11 @@ def _q3_groupjoin(lib, device, r1, n_orders_kept, lineitem, to_host,
     Consumed side: join1's result (ORDERS_TYPES), key col 1 = o_orderkey;
     the group columns [o_orderkey, o_orderdate, o_shippriority] equal the
     aggregate's (l_orderkey = o_orderkey on every match). The aggregates
-    read the lineitem scan's projections [l_orderkey, revenue, cents]."""
+    read the lineitem scan's projections [l_orderkey, revenue, cents].
+
+    producer: (join1, unscanned orders _ScanSrc) instead of r1. join1's
+    matches then go straight into the group-join's build
+    (gxop_groupjoin_build_probe_scan) and no join1 result exists."""
     gj = HashGroupJoinExec(
         lib, abi.INNER, [EquiJoinKey(1, 0, I64)],
         build_types=ORDERS_TYPES, probe_types=LINEITEM_TYPES,
@@ -138,10 +142,15 @@ def _q3_groupjoin(lib, device, r1, n_orders_kept, lineitem, to_host,
         aggs=[(abi.SUM_F64, 1), (abi.SUM_I64, 2), (abi.COUNT_ROW, -1)],
         device=device, expected_build_rows=n_orders_kept)
     try:
-        if r1:
-            lib.check(lib.lib.gxop_groupjoin_consume(
-                gj._op, C.byref(r1.contents.chunk)), "groupjoin_consume")
-        gj.build_consume()
+        if producer is not None:
+            j1, orders = producer
+            orders.kept, n_orders_kept = gj.build_probe_scan(
+                j1, orders.scan, C.byref(orders.chunk))
+        else:
+            if r1:
+                lib.check(lib.lib.gxop_groupjoin_consume(
+                    gj._op, C.byref(r1.contents.chunk)), "groupjoin_consume")
+            gj.build_consume()
         if r1:
             lib.lib.gxop_result_release(r1)
             r1 = None
@@ -198,6 +207,12 @@ def run_q3(lib, device, cust, orders, lineitem, expected_groups=0,
     try:
         _consume_src(lib, j1, cust, CUST_TYPES)
         j1.build_consume()
+        if (isinstance(orders, _ScanSrc) and isinstance(lineitem, _ScanSrc)
+                and not reshuffle_by_orderkey
+                and getattr(lib, "has_groupjoin_build_probe_scan", False)
+                and getattr(lib, "has_groupjoin_probe_scan", False)):
+            return _q3_groupjoin(lib, device, None, 0, lineitem, to_host,
+                                 keep_results, producer=(j1, orders))
         r1 = _probe_src(lib, j1, orders, ORDERS_TYPES)
         n_orders_kept = r1.contents.chunk.n_rows if r1 else 0
 

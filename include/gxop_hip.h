@@ -74,6 +74,45 @@ int gxop_groupjoin_probe_scan(gx_op *groupjoin, gx_op *scan,
                               const gx_chunk *raw_chunk,
                               int64_t *n_scan_kept, int64_t *n_matched);
 
+/* ---- producer join's matches straight into a group-join's build --------- */
+
+/* Probe `join` with the scanned rows of raw_chunk and make the result the
+ * consumed side of `groupjoin`, then build it. Exactly
+ *     gxop_join_probe_scan(join, scan, raw_chunk, &r, n_scan_kept);
+ *     gxop_groupjoin_consume(groupjoin, &r->chunk);
+ *     gxop_result_release(r);
+ *     gxop_groupjoin_build(groupjoin);
+ * Afterwards the group-join is built and holds the join's output rows with
+ * the same columns and nulls; their order (the consumed positions) is not
+ * specified. *n_consumed receives the join's output row count, *n_scan_kept
+ * the rows that passed the predicates; either may be NULL. The join's own
+ * stats advance as for gxop_join_probe_scan. Error when the group-join is
+ * already built; type mismatches are errors as in the composed calls.
+ *
+ * Fast path: after the fused probe-scan kernel has left its pair list, ONE
+ * kernel evaluates every consumed column at each pair, writes it into the
+ * group-join's build store and inserts the key, taken from the register,
+ * into the group-join's table and bloom filter: no result is materialized,
+ * copied into the store and read back. It needs
+ *   - gxop_join_probe_scan's own fast path on (join, scan, raw_chunk),
+ *   - a group-join that has consumed nothing and would build the
+ *     inline-bucket table (gxop_groupjoin_probe_scan's first condition),
+ *   - a key projection without NULLs (the raw columns it reads carry no
+ *     nulls buffer),
+ *   - at most 8 consumed columns, all I64 / I32 / F64,
+ *   - all three ops on one device and stream.
+ * GX_GJ_BUILD_FUSED=0 in the environment, read per call, forces the
+ * composed sequence. Every other shape runs it inside the library too, so
+ * the entry point is always valid. */
+int gxop_groupjoin_build_probe_scan(gx_op *groupjoin, gx_op *join,
+                                    gx_op *scan, const gx_chunk *raw_chunk,
+                                    int64_t *n_scan_kept,
+                                    int64_t *n_consumed);
+
+/* 1 when the group-join's build ran gxop_groupjoin_build_probe_scan's fast
+ * path, 0 otherwise (tests and plan diagnostics), -1 on a bad op */
+int gxop_groupjoin_build_was_fused(gx_op *groupjoin);
+
 /* cumulative probe stats of a group-join: probe_kernel_ms is event time
  * around the probing kernels, probe_launches their count, probe_rows the
  * rows probed (for a probe-scan: the scan survivors), matches the (probe
