@@ -245,6 +245,16 @@ class GxSortCfg(C.Structure):
     ]
 
 
+class GxAggLocalStats(C.Structure):
+    """gx_agg_local_stats (gxop_hip.h): the block-local accumulate path."""
+    _fields_ = [
+        ("local_rows", C.c_int64),
+        ("local_launches", C.c_int64),
+        ("local_groups_cap", C.c_int32),
+        ("replicas", C.c_int32),
+    ]
+
+
 class GxSortStats(C.Structure):
     _fields_ = [
         ("rows_consumed", C.c_int64),
@@ -267,6 +277,7 @@ EQ_NULLSAFE, NE_NULLSAFE = 7, 8
 # Projections (gx_proj_op)
 PROJ_COPY, PROJ_REV_F64, PROJ_REV_SCALED4, PROJ_Q9_AMOUNT4 = 0, 1, 2, 3
 PROJ_DEC_TO_SCALED, PROJ_SCALED_TO_DEC = 4, 5  # gx_proj.c = decimal scale
+PROJ_Q1_CHARGE6 = 6  # a * (100 - b) * (100 + c), scale 6; HIP library only
 FRAME_WHOLE_PARTITION, FRAME_ROWS_SLIDING, FRAME_ROWS_UNBOUNDED_FOLLOWING = \
     0, 1, 2
 (FRAME_RANGE_SLIDING, FRAME_RANGE_UNBOUNDED_PRECEDING,
@@ -449,6 +460,11 @@ class GxLib:
             L.gxop_sort_close.argtypes = [C.c_void_p]
         L.gxop_result_copy_col.argtypes = [C.POINTER(GxResult), C.c_int32,
                                            C.c_void_p, C.c_void_p]
+        # low-cardinality GROUP BY introspection: HIP library only
+        self.has_agg_local = hasattr(L, "gxop_agg_get_local_stats")
+        if self.has_agg_local:
+            L.gxop_agg_get_local_stats.argtypes = [
+                C.c_void_p, C.POINTER(GxAggLocalStats)]
         L.gxop_join_get_stats.argtypes = [C.c_void_p, C.POINTER(GxJoinStats)]
         L.gxop_agg_get_stats.argtypes = [C.c_void_p, C.POINTER(GxAggStats)]
         L.gxop_result_to_host.argtypes = [C.POINTER(GxResult)]

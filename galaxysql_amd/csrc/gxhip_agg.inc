@@ -722,6 +722,226 @@ __global__ void k_agg_accumulate_dec(AggAccumParams P) {
     agg_accumulate_body<true>(P);
 }
 
+/* ---- block-local pre-aggregation (few groups) ---------------------------
+ * k_agg_accumulate sends every row's RMWs to records[gid]: with a handful of
+ * groups (Q1's 4, a global aggregate's 1) all of them queue on the same few
+ * L2 lines. Here a block keeps its own copy of the `groups` records in LDS,
+ * accumulates its rows there with LDS atomics (agg_rmw itself, on the LDS
+ * record) and merges each record it touched into records[gid] once, after
+ * its last row: touched groups x stride global atomics per BLOCK instead of
+ * n_aggs per ROW. The host launches it only when every gid of the chunk is
+ * below `groups` (it knows n_groups_host), so there is no per-row fallback.
+ *
+ * Same-address LDS atomics of one instruction serialize as well, so the
+ * block holds `replicas` (a power of two, up to GX_AGG_LOCAL_MAX_REPLICAS)
+ * copies and thread t works on copy t % replicas; the flush folds the copies in registers before the one
+ * global merge. Layout: lds[(replica * groups + gid) * stride + slot], then
+ * one u32 "touched" marker per (replica, gid).
+ *
+ * Every func is a commutative monoid, so partial state folds and merges in
+ * any order; SUM_DEC / AVG_DEC keep the carry rule of agg_rmw both in LDS
+ * (returning ds add on lo) and at the merge (returning global add on lo with
+ * the partial's lo, carry + the partial's hi into hi): addition mod 2^128
+ * commutes, so the 128-bit state is exact as before. */
+#define GX_AGG_LOCAL_LDS_BYTES (32 * 1024) /* 4 blocks/CU of 160 KiB */
+#define GX_AGG_LOCAL_MAX_REPLICAS 16 /* measured: 4..16 best, 64 behind */
+
+/* Measured (profiles/README.md "Low-cardinality GROUP BY"):
+ * MAX_GROUPS: the count limit of the local group cap. The sweep has the
+ *   local path ahead up to 1024 groups, by the least there (1.15x at the
+ *   gate's chunk size); 1024 is also the reference planner's floor for the
+ *   hint when it knows nothing (HashAggExecutorFactory MIN_HASH_TABLE_SIZE),
+ *   which must not read as "few groups": 512.
+ * MIN_ROWS: chunks of 2^18 rows or more at any group count up to the cap;
+ *   MIN_ROWS_FEW: chunks of 2^16 rows or more at up to FEW_GROUPS groups
+ *   (at 2^16 rows the flush of more groups no longer pays).
+ * BLOCK_ROWS / BLOCKS_PER_CU: a block flushes touched groups x stride
+ *   atomics once, so it gets at least this many rows and the grid at most
+ *   this many blocks per CU. */
+#define GX_AGG_LOCAL_MAX_GROUPS 512
+#define GX_AGG_LOCAL_MIN_ROWS ((int64_t)1 << 18)
+#define GX_AGG_LOCAL_MIN_ROWS_FEW ((int64_t)1 << 16)
+#define GX_AGG_LOCAL_FEW_GROUPS 128
+#define GX_AGG_LOCAL_BLOCK_ROWS 2048
+#define GX_AGG_LOCAL_BLOCKS_PER_CU 4
+
+struct AggLocalParams {
+    AggAccumParams A;
+    int32_t groups;                /* every gid of the chunk is below it */
+    int32_t replicas;              /* power of two */
+    unsigned long long tmpl[3 * GX_MAX_COLS]; /* identity record */
+};
+
+__host__ __device__ static inline size_t agg_local_lds_bytes(int32_t groups,
+                                                             int32_t stride,
+                                                             int32_t replicas) {
+    return (size_t)replicas * groups * ((size_t)stride * 8 + 4);
+}
+
+/* fold one aggregate of one group over the block's replicas and merge the
+ * partial into the global record. Runs on one thread per (group, agg). */
+template <bool DEC>
+__device__ static inline void agg_local_merge(const AggLocalParams &P,
+                                              const unsigned long long *lds,
+                                              const uint32_t *touched,
+                                              int32_t g, int32_t a) {
+    const int32_t func = P.A.func[a];
+    const int32_t vo = P.A.val_off[a], so = P.A.seen_off[a];
+    const int32_t stride = P.A.stride;
+    unsigned long long acc = P.tmpl[vo], acc_hi = 0ull, seen = 0ull;
+    bool any = false;
+    for (int32_t rep = 0; rep < P.replicas; rep++) {
+        const int32_t li = rep * P.groups + g;
+        if (!touched[li]) continue;
+        any = true;
+        const unsigned long long *rec = lds + (size_t)li * stride;
+        const unsigned long long x = rec[vo];
+        if (so >= 0) seen += rec[so]; /* a flag (0/1) or AVG's count */
+        switch (func) {
+        case GX_AGG_SUM_F64: case GX_AGG_AVG_F64:
+            acc = __builtin_bit_cast(unsigned long long,
+                __builtin_bit_cast(double, acc) + __builtin_bit_cast(double, x));
+            break;
+        case GX_AGG_MIN_I64:
+            if ((long long)x < (long long)acc) acc = x;
+            break;
+        case GX_AGG_MAX_I64:
+            if ((long long)x > (long long)acc) acc = x;
+            break;
+        case GX_AGG_MIN_F64:
+            acc = __builtin_bit_cast(unsigned long long,
+                jmin_f64(__builtin_bit_cast(double, acc),
+                         __builtin_bit_cast(double, x)));
+            break;
+        case GX_AGG_MAX_F64:
+            acc = __builtin_bit_cast(unsigned long long,
+                jmax_f64(__builtin_bit_cast(double, acc),
+                         __builtin_bit_cast(double, x)));
+            break;
+        case GX_AGG_BIT_AND: acc &= x; break;
+        case GX_AGG_BIT_OR: acc |= x; break;
+        case GX_AGG_BIT_XOR: acc ^= x; break;
+        case GX_AGG_SUM_DEC: case GX_AGG_AVG_DEC:
+            if (DEC) {
+                const unsigned long long lo = acc + x;
+                acc_hi += rec[vo + 1] + (lo < acc ? 1ull : 0ull);
+                acc = lo;
+            }
+            break;
+        default: /* COUNT_ROW / COUNT_COL / SUM_I64 / SUM_I64N */
+            acc += x;
+            break;
+        }
+    }
+    if (!any) return;
+    unsigned long long *grec = P.A.records + (size_t)g * stride;
+    unsigned long long *vp = grec + vo;
+    /* a null-tracking aggregate whose inputs were all NULL here merges
+     * nothing: its identity (MIN/MAX's +-Inf, INT64_MAX/MIN) stays in LDS
+     * and `seen` stays as it was */
+    if (so >= 0 && seen == 0ull) return;
+    switch (func) {
+    case GX_AGG_COUNT_ROW: case GX_AGG_COUNT_COL: case GX_AGG_SUM_I64:
+        if (acc) atomicAdd(vp, acc);
+        break;
+    case GX_AGG_SUM_I64N:
+        atomicAdd(vp, acc);
+        if (so >= 0) grec[so] = 1ull;
+        break;
+    case GX_AGG_SUM_F64:
+        atomicAdd((double *)vp, __builtin_bit_cast(double, acc));
+        grec[so] = 1ull;
+        break;
+    case GX_AGG_AVG_F64: /* the count slot takes the partial COUNT */
+        atomicAdd((double *)vp, __builtin_bit_cast(double, acc));
+        atomicAdd(grec + so, seen);
+        break;
+    case GX_AGG_MIN_I64:
+        atomic_min_i64((long long *)vp, (long long)acc);
+        grec[so] = 1ull;
+        break;
+    case GX_AGG_MAX_I64:
+        atomic_max_i64((long long *)vp, (long long)acc);
+        grec[so] = 1ull;
+        break;
+    case GX_AGG_MIN_F64:
+        atomic_jmin_f64(vp, __builtin_bit_cast(double, acc));
+        grec[so] = 1ull;
+        break;
+    case GX_AGG_MAX_F64:
+        atomic_jmax_f64(vp, __builtin_bit_cast(double, acc));
+        grec[so] = 1ull;
+        break;
+    case GX_AGG_BIT_AND: atomicAnd(vp, acc); break;
+    case GX_AGG_BIT_OR: atomicOr(vp, acc); break;
+    case GX_AGG_BIT_XOR: atomicXor(vp, acc); break;
+    case GX_AGG_SUM_DEC:
+    case GX_AGG_AVG_DEC: {
+        if (!DEC) break;
+        /* agg_rmw's 128-bit case with v = {acc, acc_hi} */
+        const unsigned long long old = atomicAdd(vp, acc);
+        const unsigned long long add_hi =
+            acc_hi + ((old + acc) < old ? 1ull : 0ull);
+        if (add_hi != 0ull) atomicAdd(vp + 1, add_hi);
+        if (func == GX_AGG_SUM_DEC) grec[so] = 1ull;
+        else atomicAdd(grec + so, seen);
+        break; }
+    }
+}
+
+template <bool DEC>
+__device__ static inline void agg_accumulate_local_body(
+        const AggLocalParams &P) {
+    extern __shared__ unsigned long long gx_agg_lds[];
+    const int32_t stride = P.A.stride;
+    const int32_t n_recs = P.replicas * P.groups;
+    unsigned long long *lds = gx_agg_lds;
+    uint32_t *touched = (uint32_t *)(lds + (size_t)n_recs * stride);
+    for (int32_t i = threadIdx.x; i < n_recs * stride; i += blockDim.x)
+        lds[i] = P.tmpl[i % stride];
+    for (int32_t i = threadIdx.x; i < n_recs; i += blockDim.x)
+        touched[i] = 0u;
+    __syncthreads();
+
+    const int32_t rep_base =
+        (int32_t)(threadIdx.x & (uint32_t)(P.replicas - 1)) * P.groups;
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < P.A.n;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t gid = 0;
+        if (!P.A.global_group) gid = P.A.slots[P.A.slot_of_row[r]].gid;
+        if (gid >= (uint32_t)P.groups) continue; /* host contract; LDS bound */
+        const int32_t li = rep_base + (int32_t)gid;
+        unsigned long long *rec = lds + (size_t)li * stride;
+        touched[li] = 1u; /* idempotent plain store */
+        for (int a = 0; a < P.A.n_aggs; a++) {
+            if (DEC && P.A.input[a].type == GX_DECIMAL &&
+                agg_func_is_dec(P.A.func[a]))
+                agg_rmw<DEC>(P.A.func[a], rec, P.A.val_off[a],
+                             P.A.seen_off[a],
+                             agg_load_dec(P.A.input[a], r, P.A.dec_scale[a],
+                                          P.A.dec_err));
+            else
+                agg_rmw<DEC>(P.A.func[a], rec, P.A.val_off[a],
+                             P.A.seen_off[a],
+                             agg_load<DEC>(P.A.func[a], P.A.input[a], r));
+        }
+    }
+    __syncthreads(); /* the one barrier after the loop: every thread is here */
+
+    const int32_t items = P.groups * P.A.n_aggs;
+    for (int32_t i = threadIdx.x; i < items; i += blockDim.x)
+        agg_local_merge<DEC>(P, lds, touched, i / P.A.n_aggs, i % P.A.n_aggs);
+}
+
+__global__ void __launch_bounds__(256)
+k_agg_accumulate_local(AggLocalParams P) {
+    agg_accumulate_local_body<false>(P);
+}
+__global__ void __launch_bounds__(256)
+k_agg_accumulate_local_dec(AggLocalParams P) {
+    agg_accumulate_local_body<true>(P);
+}
+
 /* Emission, one kernel for the whole result: each group's record (a random
  * line in slot mode) is read ONCE and every aggregate's value + null flag
  * written from it; with packed null-free keys the group-key columns come
@@ -1049,6 +1269,14 @@ struct AggOp : gx_op {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double kernel_ms = 0.0;
     int64_t consumes = 0, rows_total = 0;
+    /* block-local pre-aggregation (k_agg_accumulate_local): GX_AGG_LOCAL at
+     * create — -1 unset (gates apply), 0 never, 1 whenever the groups fit */
+    int local_mode = -1;
+    int32_t local_cap = 0;      /* most groups the local kernel takes */
+    int32_t local_rep_max = GX_AGG_LOCAL_MAX_REPLICAS;
+    int32_t local_cus = 0;      /* CU count, read at the first launch */
+    int64_t local_rows = 0, local_launches = 0;
+    int32_t local_replicas = 0; /* at the last launch */
 
     AggOp(const gx_agg_cfg *c) : gx_op(OP_AGG, c->device, c->stream), cfg(*c) {
         group_cols_.assign(c->group_cols, c->group_cols + c->n_group_cols);
@@ -1145,6 +1373,27 @@ struct AggOp : gx_op {
             if (v >= 1 && v <= 4) slot_stride_max = v;
         }
         slot_records = stride <= slot_stride_max && cfg.n_group_cols > 0;
+        if (const char *le = getenv("GX_AGG_LOCAL")) {
+            if (le[0] == '0' && !le[1]) local_mode = 0;
+            else if (le[0] == '1' && !le[1]) local_mode = 1;
+        }
+        if (const char *re = getenv("GX_AGG_LOCAL_REPLICAS")) {
+            /* bench knob: cap the replica count (1 = plain shared copy) */
+            int v = atoi(re);
+            if (v >= 1 && v <= GX_AGG_LOCAL_MAX_REPLICAS && (v & (v - 1)) == 0)
+                local_rep_max = v;
+        }
+        local_cap = (int32_t)std::min<size_t>(
+            GX_AGG_LOCAL_MAX_GROUPS,
+            agg_local_lds_bytes(1, stride, 1) <= GX_AGG_LOCAL_LDS_BYTES
+                ? GX_AGG_LOCAL_LDS_BYTES / agg_local_lds_bytes(1, stride, 1)
+                : 0);
+        /* a planner hint of few groups: keep even a narrow state gid-indexed
+         * so its accumulate pass can run block-local (gxop.h,
+         * expected_groups) */
+        if (local_mode != 0 && cfg.expected_groups >= 1 &&
+            cfg.expected_groups <= local_cap)
+            slot_records = false;
         /* a distinct agg accumulates by gid from its own pass: state is
          * gid-indexed (gids never move) */
         if (has_distinct) slot_records = false;
@@ -1367,6 +1616,51 @@ struct AggOp : gx_op {
         return 0;
     }
 
+    /* the accumulate pass of one chunk through k_agg_accumulate_local[_dec];
+     * the caller has checked n_groups_host <= local_cap */
+    int launch_local(const AggAccumParams &AP, int64_t n) {
+        if (local_cus == 0) {
+            int v = 0;
+            HIP_OK(hipDeviceGetAttribute(
+                &v, hipDeviceAttributeMultiprocessorCount, device));
+            local_cus = v > 0 ? v : 1;
+        }
+        AggLocalParams LP;
+        LP.A = AP;
+        LP.groups = (int32_t)n_groups_host;
+        std::memcpy(LP.tmpl, tmpl, sizeof(tmpl));
+        /* as many replicas as the LDS budget holds, up to the maximum (Q1's
+         * 22-u64 record x 4 groups: 16; 128 groups of it: 1) */
+        int32_t rep = 1;
+        while (rep * 2 <= local_rep_max &&
+               agg_local_lds_bytes(LP.groups, stride, rep * 2) <=
+                   GX_AGG_LOCAL_LDS_BYTES)
+            rep *= 2;
+        LP.replicas = rep;
+        const size_t lds = agg_local_lds_bytes(LP.groups, stride, rep);
+        if (lds > GX_AGG_LOCAL_LDS_BYTES) {
+            gx_set_err("agg local: state does not fit the LDS budget");
+            return -1;
+        }
+        /* a block flushes touched groups x stride atomics once: give it
+         * GX_AGG_LOCAL_BLOCK_ROWS rows or more to spread them over, and at
+         * most GX_AGG_LOCAL_BLOCKS_PER_CU resident blocks' worth of blocks */
+        const int64_t by_rows =
+            (n + GX_AGG_LOCAL_BLOCK_ROWS - 1) / GX_AGG_LOCAL_BLOCK_ROWS;
+        const int64_t blocks = std::max<int64_t>(
+            1, std::min<int64_t>(by_rows, (int64_t)local_cus *
+                                              GX_AGG_LOCAL_BLOCKS_PER_CU));
+        auto k_local = has_dec ? k_agg_accumulate_local_dec
+                               : k_agg_accumulate_local;
+        hipLaunchKernelGGL(k_local, dim3((unsigned)blocks), dim3(256), lds,
+                           stream, LP);
+        HIP_OK(hipGetLastError());
+        local_rows += n;
+        local_launches++;
+        local_replicas = rep;
+        return 0;
+    }
+
     int consume(const gx_chunk *ch) {
         if (ensure_device(device)) return -1;
         if ((int32_t)aggs.size() > GX_MAX_COLS) { gx_set_err("too many aggs"); return -1; }
@@ -1554,7 +1848,17 @@ struct AggOp : gx_op {
             AP.n_aggs = k;
             AP.dec_err = (uint32_t *)d_decerr.p;
             auto k_accum = has_dec ? k_agg_accumulate_dec : k_agg_accumulate;
-            if (k > 0 || !has_distinct)
+            /* few groups: accumulate block-local in LDS. n_groups_host
+             * covers this chunk's gids (assigned above), so every row fits */
+            const bool local =
+                local_mode != 0 && k > 0 && n_groups_host >= 1 &&
+                (int64_t)n_groups_host <= local_cap &&
+                (local_mode == 1 || n >= GX_AGG_LOCAL_MIN_ROWS ||
+                 (n >= GX_AGG_LOCAL_MIN_ROWS_FEW &&
+                  n_groups_host <= GX_AGG_LOCAL_FEW_GROUPS));
+            if (local) {
+                if (launch_local(AP, n)) return -1;
+            } else if (k > 0 || !has_distinct)
                 hipLaunchKernelGGL(k_accum, dim3(gx_grid(n)), dim3(256), 0,
                                    stream, AP);
         }
@@ -1792,6 +2096,16 @@ int gxop_agg_get_stats(gx_op *op, gx_agg_stats *out) {
     out->consumes = a->consumes;
     out->rows = a->rows_total;
     out->groups = a->n_groups_host;
+    return 0;
+}
+
+int gxop_agg_get_local_stats(gx_op *op, gx_agg_local_stats *out) {
+    if (!op || op->kind != OP_AGG || !out) { gx_set_err("not an agg op"); return -1; }
+    AggOp *a = static_cast<AggOp *>(op);
+    out->local_rows = a->local_rows;
+    out->local_launches = a->local_launches;
+    out->local_groups_cap = a->local_cap;
+    out->replicas = a->local_replicas;
     return 0;
 }
 

@@ -163,7 +163,8 @@ __device__ static inline bool scan_row_passes(const ScanPreds &P, int64_t i) {
 }
 
 /* The value of a register-sized projection at source row `src`: a COPY of
- * an I64/I32/F64 column, REV_F64, REV_SCALED4 or Q9_AMOUNT4. The one place
+ * an I64/I32/F64 column, REV_F64, REV_SCALED4, Q9_AMOUNT4 or Q1_CHARGE6. The
+ * one place
  * these expressions are computed: proj_store (k_scan, k_gather_proj) stores
  * what this returns and the group-join probe-scan accumulates it, so all
  * three are bit-identical. A NULL input gives isnull and the value the
@@ -198,7 +199,15 @@ __device__ static inline AggVal proj_value(int32_t op, const DevColView &a,
         int64_t bv = v.isnull ? 0 : ((const int64_t *)b.values)[src];
         v.bits = (uint64_t)av * (uint64_t)(100 - bv);
         break; }
-    default: { /* GX_PROJ_Q9_AMOUNT4 */
+    case GX_PROJ_Q1_CHARGE6: {
+        v.isnull = col_is_null(a, src) || col_is_null(b, src) ||
+                   col_is_null(cc, src);
+        int64_t av = v.isnull ? 0 : ((const int64_t *)a.values)[src];
+        int64_t bv = v.isnull ? 0 : ((const int64_t *)b.values)[src];
+        int64_t cv = v.isnull ? 0 : ((const int64_t *)cc.values)[src];
+        v.bits = (uint64_t)av * (uint64_t)(100 - bv) * (uint64_t)(100 + cv);
+        break; }
+    case GX_PROJ_Q9_AMOUNT4: {
         v.isnull = col_is_null(a, src) || col_is_null(b, src) ||
                    col_is_null(cc, src) || col_is_null(dd, src);
         int64_t av = v.isnull ? 0 : ((const int64_t *)a.values)[src];
@@ -209,6 +218,9 @@ __device__ static inline AggVal proj_value(int32_t op, const DevColView &a,
             (int64_t)((uint64_t)av * (uint64_t)(100 - bv)) -
             (int64_t)((uint64_t)cv * (uint64_t)dv * 100u));
         break; }
+    default: /* not a register-sized expression: callers never pass one */
+        v.isnull = true;
+        break;
     }
     return v;
 }
@@ -241,7 +253,8 @@ __device__ static inline void proj_store(int32_t op, int32_t scale,
         break; }
     case GX_PROJ_REV_F64:
     case GX_PROJ_REV_SCALED4:
-    case GX_PROJ_Q9_AMOUNT4: {
+    case GX_PROJ_Q9_AMOUNT4:
+    case GX_PROJ_Q1_CHARGE6: {
         AggVal v = proj_value(op, a, b, cc, dd, src);
         if (out_nulls) out_nulls[at] = v.isnull;
         ((unsigned long long *)out_vals)[at] = v.bits;
@@ -746,6 +759,7 @@ struct ScanOp : gx_op {
             case GX_PROJ_COPY: out_types.push_back(input_types[p.a]); break;
             case GX_PROJ_REV_F64: out_types.push_back(GX_F64); break;
             case GX_PROJ_SCALED_TO_DEC: out_types.push_back(GX_DECIMAL); break;
+            case GX_PROJ_Q1_CHARGE6: out_types.push_back(GX_I64); break;
             default: out_types.push_back(GX_I64); break;
             }
             if (out_types.back() == GX_SLICE) has_slice_out = true;
@@ -790,10 +804,12 @@ struct ScanOp : gx_op {
         if (out_types[p] == GX_SLICE) return false;
         bool nf = !st.views[pr.a].has_nulls;
         if (pr.op == GX_PROJ_REV_F64 || pr.op == GX_PROJ_REV_SCALED4 ||
-            pr.op == GX_PROJ_Q9_AMOUNT4)
+            pr.op == GX_PROJ_Q9_AMOUNT4 || pr.op == GX_PROJ_Q1_CHARGE6)
             nf = nf && !st.views[pr.b].has_nulls;
+        if (pr.op == GX_PROJ_Q9_AMOUNT4 || pr.op == GX_PROJ_Q1_CHARGE6)
+            nf = nf && !st.views[pr.c].has_nulls;
         if (pr.op == GX_PROJ_Q9_AMOUNT4)
-            nf = nf && !st.views[pr.c].has_nulls && !st.views[pr.d].has_nulls;
+            nf = nf && !st.views[pr.d].has_nulls;
         return nf;
     }
 
@@ -830,6 +846,8 @@ struct ScanOp : gx_op {
                 P.proj_c[c] = st.views[projs[c].c];
                 P.proj_d[c] = st.views[projs[c].d];
             }
+            if (projs[c].op == GX_PROJ_Q1_CHARGE6)
+                P.proj_c[c] = st.views[projs[c].c];
             P.out_vals[c] = h->bufs[c * 2].p;
             P.out_nulls[c] = (uint8_t *)h->bufs[c * 2 + 1].p;
         }
@@ -895,8 +913,12 @@ bool probe_scan_fast_ok(const JoinOp *j, const ScanOp *s,
         if (raw->blocks[b].mem != GX_MEM_DEVICE) return false;
     const gx_proj &kp = s->projs[(size_t)j->probe_key_cols[0]];
     if (kp.op != GX_PROJ_COPY || s->input_types[kp.a] != GX_I64) return false;
+    /* Q1_CHARGE6: the fused gather's operand wiring knows the expressions
+     * it was built for; a scan with this one runs the composed sequence
+     * (so does gxop_groupjoin_build_probe_scan, which asks here first) */
     for (size_t p = 0; p < s->projs.size(); p++)
         if (s->projs[p].op == GX_PROJ_DEC_TO_SCALED ||
+            s->projs[p].op == GX_PROJ_Q1_CHARGE6 ||
             s->out_types[p] == GX_SLICE)
             return false;
     std::vector<JoinOp::OutSpec> specs = j->projected_specs();
@@ -1074,7 +1096,8 @@ bool gj_probe_scan_fast_ok(const GroupJoinOp *g, const ScanOp *s,
     const gx_proj &kp = s->projs[(size_t)g->jop->probe_key_cols[0]];
     if (kp.op != GX_PROJ_COPY || s->input_types[kp.a] != GX_I64) return false;
     for (auto &pr : s->projs)
-        if (pr.op == GX_PROJ_DEC_TO_SCALED) return false;
+        if (pr.op == GX_PROJ_DEC_TO_SCALED || pr.op == GX_PROJ_Q1_CHARGE6)
+            return false; /* Q1_CHARGE6: as in probe_scan_fast_ok */
     for (auto &sp : g->aggs) {
         if (sp.input_col < 0) continue;
         const gx_proj &pr = s->projs[(size_t)sp.input_col];
@@ -1418,11 +1441,13 @@ gx_op *gxop_scan_create(const gx_scan_cfg *cfg) {
     }
     for (int32_t i = 0; i < cfg->n_projs; i++) {
         const gx_proj &p = cfg->projs[i];
-        if (p.op < GX_PROJ_COPY || p.op > GX_PROJ_SCALED_TO_DEC ||
+        if (p.op < GX_PROJ_COPY || p.op > GX_PROJ_Q1_CHARGE6 ||
             p.a < 0 || p.a >= cfg->n_input_cols ||
             ((p.op == GX_PROJ_REV_F64 || p.op == GX_PROJ_REV_SCALED4 ||
-              p.op == GX_PROJ_Q9_AMOUNT4) &&
-             (p.b < 0 || p.b >= cfg->n_input_cols))) {
+              p.op == GX_PROJ_Q9_AMOUNT4 || p.op == GX_PROJ_Q1_CHARGE6) &&
+             (p.b < 0 || p.b >= cfg->n_input_cols)) ||
+            (p.op == GX_PROJ_Q1_CHARGE6 &&
+             (p.c < 0 || p.c >= cfg->n_input_cols))) {
             gx_set_err("bad scan projection (op or column)");
             return nullptr;
         }

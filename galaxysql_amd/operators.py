@@ -223,6 +223,22 @@ class HashAggExec:
         return {"kernel_ms": s.kernel_ms, "consumes": s.consumes,
                 "rows": s.rows, "groups": s.groups}
 
+    def local_stats(self):
+        """The block-local (LDS) accumulate path of the HIP library:
+        local_rows / local_launches through it, the most groups it takes for
+        this op (local_groups_cap) and the replicas of its last launch."""
+        from .abi import GxAggLocalStats
+        if not getattr(self._lib, "has_agg_local", False):
+            raise RuntimeError("gxop_agg_get_local_stats: not in this library")
+        s = GxAggLocalStats()
+        self._lib.check(
+            self._lib.lib.gxop_agg_get_local_stats(self._op, C.byref(s)),
+            "agg_get_local_stats")
+        return {"local_rows": s.local_rows,
+                "local_launches": s.local_launches,
+                "local_groups_cap": s.local_groups_cap,
+                "replicas": s.replicas}
+
     def build_consume(self):
         self._lib.check(self._lib.lib.gxop_agg_build(self._op), "agg_build")
 

@@ -912,3 +912,191 @@ def gen_q9_numpy(rng, n_part, n_supp, n_orders, n_lineitem, n_nation=25):
                 rng.integers(100, 10_000_000, n_lineitem).astype(np.int64),
                 rng.integers(0, 11, n_lineitem).astype(np.int64)]
     return part, supplier, partsupp, orders, lineitem
+
+
+# ---- Q1: pricing summary report ------------------------------------------
+# SELECT l_returnflag, l_linestatus, SUM(qty), SUM(extprice),
+#        SUM(extprice*(1-disc)), SUM(extprice*(1-disc)*(1+tax)),
+#        AVG(qty), AVG(extprice), AVG(disc), COUNT(*)
+# FROM lineitem WHERE l_shipdate <= date '1998-12-01' - 90 days
+# GROUP BY l_returnflag, l_linestatus ORDER BY l_returnflag, l_linestatus
+#
+# ~98% of lineitem into 4 groups: the low-cardinality end of GROUP BY, which
+# the aggregation runs block-local in LDS (gxop_hip.h, gx_agg_local_stats).
+# Flags are dictionary codes (A/N/R -> 0/1/2, F/O -> 0/1), money is exact:
+# quantity at scale 2, extendedprice in cents, discount / tax in hundredths.
+
+# l_returnflag, l_linestatus, l_shipdate (days), l_quantity, l_extendedprice,
+# l_discount, l_tax
+Q1_LINEITEM_TYPES = [I32, I32, I32, I64, I64, I64, I64]
+Q1_CUTOFF_DAYS = 10471           # 1998-09-02, days since 1970-01-01
+Q1_SCAN_PROJS = [(abi.PROJ_COPY, 0), (abi.PROJ_COPY, 1), (abi.PROJ_COPY, 3),
+                 (abi.PROJ_COPY, 4), (abi.PROJ_REV_SCALED4, 4, 5),
+                 (abi.PROJ_Q1_CHARGE6, 4, 5, 6), (abi.PROJ_COPY, 5)]
+# flag, status, qty, price, disc_price (scale 4), charge (scale 6), disc
+Q1_SCAN_TYPES = [I32, I32, I64, I64, I64, I64, I64]
+
+
+def q1_aggs():
+    return [(abi.sum_dec(2), 2), (abi.sum_dec(2), 3), (abi.sum_dec(4), 4),
+            (abi.sum_dec(6), 5), (abi.avg_dec(2), 2), (abi.avg_dec(2), 3),
+            (abi.avg_dec(2), 6), (abi.COUNT_ROW, -1)]
+
+
+def gen_q1_numpy(rng, n, nulls=False):
+    """n lineitem rows as (values, nulls_or_None) per Q1_LINEITEM_TYPES
+    column. Populations as TPC-H's: rows shipped after 1995-06-17 are N/O,
+    earlier ones A/F or R/F, with a rare N/F. nulls=True marks ~5% of each
+    measure and ~2% of the ship dates NULL (a NULL date fails the filter)."""
+    import numpy as np
+    ship = rng.integers(8036, 10562, n).astype(np.int32)   # 1992-01-02..
+    late = ship > 9298                                     # 1995-06-17
+    status = late.astype(np.int32)                         # F = 0, O = 1
+    early_flag = np.where(rng.random(n) < 0.5, 0, 2)       # A = 0, R = 2
+    early_flag = np.where(rng.random(n) < 0.002, 1, early_flag)
+    flag = np.where(late, 1, early_flag).astype(np.int32)  # N = 1
+    qty = (rng.integers(1, 51, n) * 100).astype(np.int64)
+    price = rng.integers(90_000, 10_500_000, n).astype(np.int64)
+    disc = rng.integers(0, 11, n).astype(np.int64)
+    tax = rng.integers(0, 9, n).astype(np.int64)
+
+    def nul(frac):
+        return (rng.random(n) < frac).astype(np.uint8) if nulls else None
+
+    return [(flag, None), (status, None), (ship, nul(0.02)), (qty, nul(0.05)),
+            (price, nul(0.05)), (disc, nul(0.05)), (tax, nul(0.05))]
+
+
+def _avg4_half_up(total, count, scale):
+    """total x 10^-scale / count, rounded half-up on the magnitude, as a
+    scale-4 integer (what AVG_DEC emits)."""
+    num = abs(total) * 10 ** (4 - scale)
+    q = (2 * num + count) // (2 * count)
+    return -q if total < 0 else q
+
+
+def ref_q1_numpy(cols, cutoff=Q1_CUTOFF_DAYS):
+    """Q1 over gen_q1_numpy columns in Python integers. Rows in ORDER BY
+    order: (flag, status, sum_qty, sum_price, sum_disc_price, sum_charge,
+    avg_qty, avg_price, avg_disc, count); a DECIMAL cell is (scaled value,
+    scale), or None where every input of the group was NULL."""
+    import numpy as np
+
+    def isnull(c):
+        return (np.zeros(len(c[0]), dtype=bool) if c[1] is None
+                else np.asarray(c[1]).astype(bool))
+
+    flag, status, ship, qty, price, disc, tax = cols
+    keep = ~isnull(ship) & (ship[0] <= cutoff)
+    nq, np_, nd, nt = isnull(qty), isnull(price), isnull(disc), isnull(tax)
+    dp_null = np_ | nd
+    ch_null = dp_null | nt
+    p, d, t = (price[0].astype(object), disc[0].astype(object),
+               tax[0].astype(object))
+    disc_price = p * (100 - d)
+    charge = disc_price * (100 + t)
+
+    def agg(vals, valid, scale, avg=False):
+        cnt = int(valid.sum())
+        if cnt == 0:
+            return None
+        total = sum(int(v) for v in vals[valid])
+        if avg:
+            return (_avg4_half_up(total, cnt, scale), 4)
+        return (total, scale)
+
+    rows = []
+    for f, s in sorted(set(zip(flag[0][keep].tolist(),
+                               status[0][keep].tolist()))):
+        m = keep & (flag[0] == f) & (status[0] == s)
+        rows.append((f, s,
+                     agg(qty[0], m & ~nq, 2), agg(price[0], m & ~np_, 2),
+                     agg(disc_price, m & ~dp_null, 4),
+                     agg(charge, m & ~ch_null, 6),
+                     agg(qty[0], m & ~nq, 2, True),
+                     agg(price[0], m & ~np_, 2, True),
+                     agg(disc[0], m & ~nd, 2, True), int(m.sum())))
+    return rows
+
+
+def _q1_slices(lib, raw_lineitem, chunk_rows):
+    """(gx_chunk, keepalive) per chunk_rows rows of raw_lineitem: numpy
+    (values, nulls_or_None) pairs (host chunks) or torch tensors (null-free,
+    host or device, no copy)."""
+    from .chunk import Block, Chunk
+    first = raw_lineitem[0]
+    pairs = isinstance(first, tuple)
+    n = len(first[0]) if pairs else first.numel()
+    for a in range(0, n, chunk_rows):
+        b = min(a + chunk_rows, n)
+        ka = []
+        if pairs:
+            ch = Chunk([Block(t, values=v[a:b],
+                              nulls=None if nl is None else nl[a:b])
+                        for t, (v, nl) in zip(Q1_LINEITEM_TYPES,
+                                              raw_lineitem)])
+            ka.append(ch)
+            yield lib.to_gx_chunk(ch, ka), ka
+        else:
+            yield chunk_from_torch(lib, [t[a:b] for t in raw_lineitem],
+                                   Q1_LINEITEM_TYPES, ka), ka
+
+
+def run_q1(lib, device, raw_lineitem, chunk_rows=1 << 24, to_host=True,
+           cutoff=Q1_CUTOFF_DAYS):
+    """Scan (filter + the four expressions) -> hash aggregation on the two
+    codes -> sort, fed chunk_rows raw rows at a time so the projected chunk
+    stays bounded. Returns (result chunks in ORDER BY order, info); the
+    DECIMAL columns decode with chunk.dec40_decode_wide. to_host=False drains
+    the result on the device and returns no chunks."""
+    from .operators import ScanExec, SortExec
+    scan = ScanExec(lib, [(2, abi.LE, cutoff)], Q1_SCAN_PROJS,
+                    Q1_LINEITEM_TYPES, device=device)
+    agg = HashAggExec(lib, group_cols=[0, 1], aggs=q1_aggs(),
+                      input_types=Q1_SCAN_TYPES, expected_groups=6,
+                      device=device)
+    out_types = [I32, I32] + [abi.DECIMAL] * 7 + [I64]
+    sort = SortExec(lib, [(0, True), (1, True)], out_types, device=device)
+    kept = 0
+    try:
+        for gc, _ka in _q1_slices(lib, raw_lineitem, chunk_rows):
+            r = scan.consume_raw(C.byref(gc))
+            if not r:
+                continue
+            try:
+                kept += r.contents.chunk.n_rows
+                lib.check(lib.lib.gxop_agg_consume(
+                    agg._op, C.byref(r.contents.chunk)), "agg_consume")
+            finally:
+                lib.lib.gxop_result_release(r)
+        agg.build_consume()
+        while True:
+            out = C.POINTER(GxResult)()
+            lib.check(lib.lib.gxop_agg_next(agg._op, C.byref(out)),
+                      "agg_next")
+            if not out:
+                break
+            try:
+                sort.consume_raw(C.byref(out.contents.chunk))
+            finally:
+                lib.lib.gxop_result_release(out)
+        sort.build_consume()
+        info = {"lineitem_kept": kept,
+                "local_rows": agg.local_stats()["local_rows"],
+                "agg_kernel_ms": agg.stats()["kernel_ms"]}
+        chunks = []
+        if to_host:
+            chunks = sort.result_chunks()
+        else:
+            while True:
+                out = C.POINTER(GxResult)()
+                lib.check(lib.lib.gxop_sort_next(sort._op, C.byref(out)),
+                          "sort_next")
+                if not out:
+                    break
+                lib.lib.gxop_result_release(out)
+        return chunks, info
+    finally:
+        sort.close()
+        agg.close()
+        scan.close()

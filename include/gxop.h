@@ -371,7 +371,15 @@ typedef struct gx_agg_cfg {
     const gx_agg_spec *aggs;
     int32_t n_input_cols;
     const int32_t *input_types;   /* gx_type per input column */
-    int64_t expected_groups;      /* size hint; 0 = unknown */
+    int64_t expected_groups;      /* size hint; 0 = unknown. HIP library: a
+                                     hint of 1..local_groups_cap (gxop_hip.h,
+                                     gx_agg_local_stats) also keeps a narrow
+                                     state (<= 4 u64) gid-indexed, so that
+                                     its accumulate pass runs block-local in
+                                     LDS instead of fused into the insert. A
+                                     small hint that turns out wrong costs
+                                     that fusion (the op stays on the
+                                     two-pass path); results are the same */
     int32_t device;
     uint64_t stream;
 } gx_agg_cfg;
@@ -617,8 +625,14 @@ typedef enum gx_proj_op {
                               cents/hundredths -> DECIMAL scale-4, exact */
     GX_PROJ_DEC_TO_SCALED = 4, /* a = GX_DECIMAL col (simple format),
                                   c = scale -> exact scaled i64 */
-    GX_PROJ_SCALED_TO_DEC = 5  /* a = scaled i64 col, c = scale ->
+    GX_PROJ_SCALED_TO_DEC = 5, /* a = scaled i64 col, c = scale ->
                                   GX_DECIMAL (DecimalBox simple layout) */
+    GX_PROJ_Q1_CHARGE6 = 6     /* out = a * (100 - b) * (100 + c): Q1 charge =
+                                  extprice*(1-disc)*(1+tax), i64 cents x
+                                  hundredths x hundredths -> DECIMAL scale-6,
+                                  exact; NULL if any input is. HIP library
+                                  only: the CPU oracle rejects op 6 at
+                                  create */
 } gx_proj_op;
 
 typedef struct gx_proj {

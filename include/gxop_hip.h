@@ -119,6 +119,31 @@ int gxop_groupjoin_build_was_fused(gx_op *groupjoin);
  * row, consumed position) matches accumulated */
 int gxop_groupjoin_get_stats(gx_op *groupjoin, gx_join_stats *out);
 
+/* ---- low-cardinality GROUP BY: block-local pre-aggregation -------------- */
+
+/* A gid-indexed aggregation (wide state, the global aggregate, the plain
+ * aggregates of an op with DISTINCT ones, or a narrow state created with a
+ * small expected_groups, see gx_agg_cfg) whose group count is at most
+ * local_groups_cap accumulates a chunk of 2^18 rows or more (2^16 or more
+ * with up to 128 groups) per block in LDS and merges each block's partial
+ * records into the group records once, instead of one global atomic per row
+ * and aggregate on the same few lines.
+ * Results are the same rows (f64 sums within the usual reordering).
+ * GX_AGG_LOCAL in the environment at create: 0 = never, 1 = whenever the
+ * group count fits, at any chunk size; unset = the gates above.
+ *
+ * local_rows: rows accumulated through that kernel; local_launches: its
+ * launches; local_groups_cap: the most groups it takes for this op's record
+ * size; replicas: LDS copies of the state per block at the last launch. */
+typedef struct gx_agg_local_stats {
+    int64_t local_rows;
+    int64_t local_launches;
+    int32_t local_groups_cap;
+    int32_t replicas;
+} gx_agg_local_stats;
+
+int gxop_agg_get_local_stats(gx_op *agg, gx_agg_local_stats *out);
+
 /* ---- sort / top-N (ORDER BY ... [LIMIT offset, fetch]) ------------------ */
 
 /* SortExec / SpilledTopNExec / LimitExec in one operator: consume chunks,
