@@ -30,6 +30,7 @@
  */
 #include "gx_common.h"
 #include "gx_dec128.h"
+#include "gx_agg_layout.h" /* GX_MAX_COLS, the aggregate state record */
 
 #include <algorithm>
 #include <cstdlib>
@@ -43,7 +44,6 @@ thread_local std::string gx_err;
 /* ================= kernel-side column descriptors ====================== */
 
 #define GX_MAX_KEYS 4
-#define GX_MAX_COLS 16
 
 struct KeyViews {
     int32_t n;

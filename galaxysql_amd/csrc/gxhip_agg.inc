@@ -163,6 +163,10 @@ struct AggAccumParams {
     int64_t base_krow;
     int64_t n;
     int global_group;          /* noGroupBy: everything is gid 0 */
+    /* The aggregates applied: an AggRecDesc's five fields, loose. Embedding
+     * the struct here keeps the bytes but changes how the kernel-argument
+     * loads of k_agg_accumulate_local are split (24 VGPRs for 28,
+     * profiles/README.md), so set_desc copies them instead. */
     int32_t n_aggs;
     int32_t stride;            /* record size in u64s */
     int32_t func[GX_MAX_COLS];
@@ -174,6 +178,14 @@ struct AggAccumParams {
      * only): the scale each record is brought to, the sticky fence word */
     uint8_t dec_scale[GX_MAX_COLS];
     uint32_t *dec_err;
+
+    void set_desc(const AggRecDesc &R) {
+        n_aggs = R.n_aggs;
+        stride = R.stride;
+        std::memcpy(func, R.func, sizeof(func));
+        std::memcpy(val_off, R.val_off, sizeof(val_off));
+        std::memcpy(seen_off, R.seen_off, sizeof(seen_off));
+    }
 };
 
 /* One aggregate input value: `bits` holds an I64 value, a sign-extended I32
@@ -193,10 +205,6 @@ __device__ static inline int64_t aggval_i64(const AggVal &v) {
 __device__ static inline double aggval_f64(const AggVal &v) {
     return v.type == GX_F64 ? __builtin_bit_cast(double, v.bits)
                             : (double)(int64_t)v.bits;
-}
-
-__host__ __device__ static inline bool agg_func_is_dec(int32_t func) {
-    return func == GX_AGG_SUM_DEC || func == GX_AGG_AVG_DEC;
 }
 
 /* the value an aggregate of `func` reads from column c at row r (COUNT
@@ -336,19 +344,10 @@ __device__ static inline void agg_rmw(int32_t func, unsigned long long *rec,
  * under the mask of f64 slots and one u64 atomicAdd under the mask of
  * integer slots. The "seen" slot of a null-tracking SUM is ADDED 1 here
  * (it rides in the integer instruction) where agg_rmw stores 1: every
- * reader tests it against zero only, AVG's is a count either way. */
+ * reader tests it against zero only, AVG's is a count either way. Which
+ * funcs are additive: agg_func_additive (SUM_DEC / AVG_DEC are not, their
+ * carry needs agg_rmw's returning add). */
 #define GX_AGG_T_SLOTS 4
-
-/* SUM_DEC / AVG_DEC are NOT additive in this sense: their carry needs the
- * returning add of agg_rmw, the transposed path sends non-returning ones */
-__host__ __device__ static inline bool agg_func_additive(int32_t func) {
-    return func == GX_AGG_COUNT_ROW || func == GX_AGG_COUNT_COL ||
-           func == GX_AGG_SUM_I64 || func == GX_AGG_SUM_I64N ||
-           func == GX_AGG_SUM_F64 || func == GX_AGG_AVG_F64;
-}
-__host__ __device__ static inline bool agg_func_adds_f64(int32_t func) {
-    return func == GX_AGG_SUM_F64 || func == GX_AGG_AVG_F64;
-}
 
 /* what one contribution adds to each slot of its record: bit s of `skip`
  * set = nothing (slot past the record, NULL input, idle lane) */
@@ -438,9 +437,9 @@ __device__ static inline void agg_add_transposed(unsigned long long *records,
  * high word of agg_load and the 40-B record decode exist only there, so the
  * kernels every other op runs are compiled as if the funcs did not exist. */
 template <bool DEC = false>
-__device__ static inline void agg_apply(const AggAccumParams &P, uint32_t gid,
-                                        int64_t r) {
-    unsigned long long *rec = P.records + (size_t)gid * P.stride;
+__device__ static inline void agg_apply_rec(const AggAccumParams &P,
+                                            unsigned long long *rec,
+                                            int64_t r) {
     for (int a = 0; a < P.n_aggs; a++) {
         if (DEC && P.input[a].type == GX_DECIMAL &&
             agg_func_is_dec(P.func[a]))
@@ -451,6 +450,13 @@ __device__ static inline void agg_apply(const AggAccumParams &P, uint32_t gid,
             agg_rmw<DEC>(P.func[a], rec, P.val_off[a], P.seen_off[a],
                          agg_load<DEC>(P.func[a], P.input[a], r));
     }
+}
+
+/* row r into the global record of group / slot / position `gid` */
+template <bool DEC = false>
+__device__ static inline void agg_apply(const AggAccumParams &P, uint32_t gid,
+                                        int64_t r) {
+    agg_apply_rec<DEC>(P, P.records + (size_t)gid * P.stride, r);
 }
 
 struct AggInsertParams {
@@ -699,6 +705,41 @@ __global__ void k_agg_init(AggInitParams P) {
         P.records[P.from * P.stride + i] = P.tmpl[i % P.stride];
 }
 
+/* identity-initialize records [from, to) of buf, laid out by L */
+static inline void agg_launch_init(const AggLayout &L, void *buf, int64_t from,
+                                   int64_t to, hipStream_t stream) {
+    if (to <= from) return;
+    AggInitParams P;
+    P.records = (unsigned long long *)buf;
+    P.stride = L.desc.stride;
+    P.from = from;
+    P.to = to;
+    std::memcpy(P.tmpl, L.tmpl, sizeof(P.tmpl));
+    hipLaunchKernelGGL(k_agg_init, dim3(gx_grid((to - from) * P.stride)),
+                       dim3(256), 0, stream, P);
+}
+
+/* the layout of an op's aggregate list (base funcs, <= GX_MAX_COLS) */
+static inline AggLayout agg_layout_of(const std::vector<gx_agg_spec> &aggs) {
+    int32_t funcs[GX_MAX_COLS];
+    for (size_t a = 0; a < aggs.size(); a++) funcs[a] = aggs[a].func;
+    AggLayout L;
+    L.build(funcs, (int)aggs.size());
+    return L;
+}
+
+/* dst[i] = the staged column aggregate i of a descriptor reads; COUNT(*)'s
+ * stays as the caller zeroed it. agg_idx: the list the descriptor was
+ * select()ed by, NULL = every aggregate of the op. */
+static inline void agg_bind_inputs(DevColView *dst, const gx_agg_spec *aggs,
+                                   const int32_t *agg_idx, int n,
+                                   const std::vector<DevColView> &views) {
+    for (int i = 0; i < n; i++) {
+        const int32_t col = aggs[agg_idx ? agg_idx[i] : i].input_col;
+        if (col >= 0) dst[i] = views[(size_t)col];
+    }
+}
+
 template <bool DEC>
 __device__ static inline void agg_accumulate_body(const AggAccumParams &P) {
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < P.n;
@@ -913,24 +954,14 @@ __device__ static inline void agg_accumulate_local_body(
         const int32_t li = rep_base + (int32_t)gid;
         unsigned long long *rec = lds + (size_t)li * stride;
         touched[li] = 1u; /* idempotent plain store */
-        for (int a = 0; a < P.A.n_aggs; a++) {
-            if (DEC && P.A.input[a].type == GX_DECIMAL &&
-                agg_func_is_dec(P.A.func[a]))
-                agg_rmw<DEC>(P.A.func[a], rec, P.A.val_off[a],
-                             P.A.seen_off[a],
-                             agg_load_dec(P.A.input[a], r, P.A.dec_scale[a],
-                                          P.A.dec_err));
-            else
-                agg_rmw<DEC>(P.A.func[a], rec, P.A.val_off[a],
-                             P.A.seen_off[a],
-                             agg_load<DEC>(P.A.func[a], P.A.input[a], r));
-        }
+        agg_apply_rec<DEC>(P.A, rec, r); /* agg_rmw's atomics, on LDS */
     }
     __syncthreads(); /* the one barrier after the loop: every thread is here */
 
     const int32_t items = P.groups * P.A.n_aggs;
     for (int32_t i = threadIdx.x; i < items; i += blockDim.x)
-        agg_local_merge<DEC>(P, lds, touched, i / P.A.n_aggs, i % P.A.n_aggs);
+        agg_local_merge<DEC>(P, lds, touched, i / P.A.n_aggs,
+                             i % P.A.n_aggs);
 }
 
 __global__ void __launch_bounds__(256)
@@ -949,13 +980,9 @@ k_agg_accumulate_local_dec(AggLocalParams P) {
  * instead of one gather per key column). */
 struct AggEmitParams {
     const unsigned long long *records;
-    int32_t stride;
     uint32_t n_groups;
     const uint32_t *slot_of_gid;   /* slot mode; NULL = records[gid] */
-    int32_t n_aggs;
-    int32_t func[GX_MAX_COLS];
-    int32_t val_off[GX_MAX_COLS];
-    int32_t seen_off[GX_MAX_COLS];
+    AggRecDesc R;
     uint8_t dec_scale[GX_MAX_COLS];  /* SUM_DEC / AVG_DEC: input scale */
     void *out_vals[GX_MAX_COLS];
     uint8_t *out_nulls[GX_MAX_COLS];
@@ -990,12 +1017,12 @@ __global__ void k_agg_emit(AggEmitParams P) {
             }
         }
         const size_t rec_idx = P.slot_of_gid ? P.slot_of_gid[g] : g;
-        const unsigned long long *rec = P.records + rec_idx * P.stride;
-        for (int a = 0; a < P.n_aggs; a++) {
-            const int32_t func = P.func[a], seen_off = P.seen_off[a];
-            bool isnull = seen_off >= 0 && rec[seen_off] == 0ull;
-            P.out_nulls[a][g] = isnull;
+        const unsigned long long *rec = P.records + rec_idx * P.R.stride;
+        for (int a = 0; a < P.R.n_aggs; a++) {
+            const int32_t func = P.R.func[a], seen_off = P.R.seen_off[a];
             if (agg_func_is_dec(func)) {
+                const bool isnull = rec[seen_off] == 0ull;
+                P.out_nulls[a][g] = isnull;
                 /* 40-B DecimalBlock record of the 128-bit state; AVG
                  * divides |sum| by the count, half-up at scale 4 */
                 uint8_t *dst = (uint8_t *)P.out_vals[a] + (size_t)g * 40;
@@ -1005,8 +1032,8 @@ __global__ void k_agg_emit(AggEmitParams P) {
                     continue;
                 }
                 gx_u128 mag;
-                mag.lo = rec[P.val_off[a]];
-                mag.hi = rec[P.val_off[a] + 1];
+                mag.lo = rec[P.R.val_off[a]];
+                mag.hi = rec[P.R.val_off[a] + 1];
                 const bool neg = (mag.hi >> 63) != 0ull;
                 if (neg) mag = gx_u128_neg(mag);
                 int scale = P.dec_scale[a];
@@ -1017,17 +1044,11 @@ __global__ void k_agg_emit(AggEmitParams P) {
                 gx_u128_to_dec40(mag, neg, scale, dst);
                 continue;
             }
-            bool f64 = func == GX_AGG_SUM_F64 || func == GX_AGG_MIN_F64 ||
-                       func == GX_AGG_MAX_F64 || func == GX_AGG_AVG_F64;
-            unsigned long long v = isnull ? 0ull : rec[P.val_off[a]];
-            if (func == GX_AGG_AVG_F64)
-                ((double *)P.out_vals[a])[g] = isnull ? 0.0
-                    : __builtin_bit_cast(double, v) / (double)rec[seen_off];
-            else if (f64)
-                ((double *)P.out_vals[a])[g] =
-                    isnull ? 0.0 : __builtin_bit_cast(double, v);
-            else
-                ((int64_t *)P.out_vals[a])[g] = (int64_t)v;
+            /* I64 results and F64 bit patterns alike */
+            const AggDecoded d = agg_decode(func, rec, P.R.val_off[a],
+                                            seen_off);
+            P.out_nulls[a][g] = d.isnull;
+            ((unsigned long long *)P.out_vals[a])[g] = d.bits;
         }
     }
 }
@@ -1248,17 +1269,14 @@ struct AggOp : gx_op {
     DevBuf d_nullmask, d_packed;  /* packed fast-path key records */
     DevStore keystore;         /* appended group-key columns (for emit) */
     bool slot_records = false; /* records indexed by slot (narrow state) */
-    bool tmpl_zero = true;     /* identity record is all zero bits */
+    AggLayout layout;          /* the AoS state record, over aggs[] */
+    std::vector<int32_t> plain_idx; /* the aggs no DistSet feeds */
     /* SUM_DEC / AVG_DEC: aggs[] holds the base func, the scale that rode in
      * the spec's upper 16 bits is split off here once */
     uint8_t dec_scale[GX_MAX_COLS] = {0};
     bool has_dec = false;       /* consume launches the *_dec kernels */
     bool has_dec_input = false; /* one of them reads a GX_DECIMAL column:
                                    consume reads the fence word back */
-    int32_t stride = 0;        /* record size in u64s */
-    int32_t val_off[GX_MAX_COLS] = {0};
-    int32_t seen_off[GX_MAX_COLS] = {0};
-    unsigned long long tmpl[3 * GX_MAX_COLS] = {0};
     int64_t n_slots = 0;
     uint32_t mask = 0;
     uint32_t n_groups_host = 0;
@@ -1328,40 +1346,10 @@ struct AggOp : gx_op {
                      && group_cols_.size() >= 2;
         keystore.init((int32_t)key_types.size(), key_types.data(), stream);
 
-        /* AoS record layout: one u64 value slot per agg (two for the 128-bit
-         * SUM_DEC / AVG_DEC sum) + one u64 seen slot for null-tracking aggs
-         * (AVG's is its count), identity-initialized. */
-        int32_t off = 0;
-        for (size_t a = 0; a < aggs.size(); a++) {
-            val_off[a] = off;
-            switch (aggs[a].func) {
-            case GX_AGG_MIN_I64: tmpl[off] = (unsigned long long)INT64_MAX; break;
-            case GX_AGG_MAX_I64: tmpl[off] = (unsigned long long)INT64_MIN; break;
-            case GX_AGG_MIN_F64: tmpl[off] = __builtin_bit_cast(unsigned long long, (double)INFINITY); break;
-            case GX_AGG_MAX_F64: tmpl[off] = __builtin_bit_cast(unsigned long long, (double)-INFINITY); break;
-            case GX_AGG_BIT_AND: tmpl[off] = ~0ull; break;
-            default: tmpl[off] = 0ull; break;
-            }
-            off++;
-            if (agg_func_is_dec(aggs[a].func)) /* {lo, hi}: hi follows lo */
-                tmpl[off++] = 0ull;
-            bool tracks_null = !(aggs[a].func == GX_AGG_COUNT_ROW ||
-                                 aggs[a].func == GX_AGG_COUNT_COL ||
-                                 aggs[a].func == GX_AGG_SUM_I64 ||
-                                 aggs[a].func == GX_AGG_BIT_AND ||
-                                 aggs[a].func == GX_AGG_BIT_OR ||
-                                 aggs[a].func == GX_AGG_BIT_XOR);
-            if (tracks_null) {
-                seen_off[a] = off;
-                tmpl[off] = 0ull;
-                off++;
-            } else {
-                seen_off[a] = -1;
-            }
-        }
-        stride = off > 0 ? off : 1;
-        for (int32_t k = 0; k < stride; k++)
-            if (tmpl[k] != 0ull) tmpl_zero = false;
+        layout = agg_layout_of(aggs);
+        for (size_t a = 0; a < aggs.size(); a++)
+            if (!is_distinct[a]) plain_idx.push_back((int32_t)a);
+        const int32_t stride = layout.desc.stride;
         /* slot-indexed state: the accumulate RMW lands on records[slot]
          * directly (one random line/row) and fuses into the insert pass.
          * Memory = n_slots x stride x 8 (2x the group count at load 0.5),
@@ -1408,19 +1396,13 @@ struct AggOp : gx_op {
     /* identity-initialize records [from, to) of buf */
     int init_records(void *buf, int64_t from, int64_t to) {
         if (to <= from) return 0;
-        if (tmpl_zero) {
-            HIP_OK(hipMemsetAsync((char *)buf + (size_t)from * stride * 8, 0,
-                                  (size_t)(to - from) * stride * 8, stream));
+        if (layout.tmpl_zero) {
+            const size_t rec_bytes = (size_t)layout.desc.stride * 8;
+            HIP_OK(hipMemsetAsync((char *)buf + (size_t)from * rec_bytes, 0,
+                                  (size_t)(to - from) * rec_bytes, stream));
             return 0;
         }
-        AggInitParams P;
-        P.records = (unsigned long long *)buf;
-        P.stride = stride;
-        P.from = from;
-        P.to = to;
-        std::memcpy(P.tmpl, tmpl, sizeof(tmpl));
-        hipLaunchKernelGGL(k_agg_init, dim3(gx_grid((to - from) * stride)),
-                           dim3(256), 0, stream, P);
+        agg_launch_init(layout, buf, from, to, stream);
         return 0;
     }
     int init_state_range(int64_t from, int64_t to) {
@@ -1436,25 +1418,25 @@ struct AggOp : gx_op {
             group_cap = ncap;
             return 0;
         }
-        if (d_records.grow((size_t)ncap * stride * 8, stream)) return -1;
+        if (d_records.grow((size_t)ncap * layout.desc.stride * 8, stream))
+            return -1;
         int64_t old = group_cap;
         group_cap = ncap;
         return init_state_range(old, ncap);
     }
 
-    /* fused-accumulate params: only the fields agg_apply reads */
-    void fill_accum_params(AggAccumParams &A, const StagedChunk &st) {
-        std::memset(&A, 0, sizeof(A));
-        A.n_aggs = (int32_t)aggs.size();
-        A.stride = stride;
+    /* the fields agg_apply reads: aggregates idx[0..k) of the op, or all of
+     * them (idx == NULL), over the staged chunk. The one place where an
+     * index list meets both select() and the input binding. */
+    void fill_accum_params(AggAccumParams &A, const StagedChunk &st,
+                           const int32_t *idx = nullptr, int k = 0) {
+        A.set_desc(idx ? layout.select(idx, k) : layout.desc);
+        std::memset(A.input, 0, sizeof(A.input)); /* COUNT(*) binds none */
+        std::memset(A.dec_scale, 0, sizeof(A.dec_scale));
+        agg_bind_inputs(A.input, aggs.data(), idx, A.n_aggs, st.views);
+        for (int i = 0; i < A.n_aggs; i++)
+            A.dec_scale[i] = dec_scale[idx ? idx[i] : i];
         A.records = (unsigned long long *)d_records.p;
-        for (size_t a = 0; a < aggs.size(); a++) {
-            A.func[a] = aggs[a].func;
-            A.val_off[a] = val_off[a];
-            A.seen_off[a] = seen_off[a];
-            A.dec_scale[a] = dec_scale[a];
-            if (aggs[a].input_col >= 0) A.input[a] = st.views[aggs[a].input_col];
-        }
         A.dec_err = (uint32_t *)d_decerr.p;
     }
 
@@ -1481,6 +1463,7 @@ struct AggOp : gx_op {
          * ladder pays a full-chunk insert rerun per step */
         if (force_double) ns = std::max<int64_t>(ns, n_slots * 4);
         if (ns <= n_slots) return 0;
+        const int32_t stride = layout.desc.stride;
         DevBuf new_slots, new_records;
         if (new_slots.grow((size_t)ns * sizeof(AggSlot), stream)) return -1;
         HIP_OK(hipMemsetAsync(new_slots.p, 0, (size_t)ns * sizeof(AggSlot), stream));
@@ -1583,16 +1566,9 @@ struct AggOp : gx_op {
         IP.n = n;
         IP.status = (uint8_t *)d_dstatus.p;
         IP.ctl = (uint32_t *)ds.d_ctl.p;
-        IP.A.n_aggs = (int32_t)ds.agg_idx.size();
-        IP.A.stride = stride;
-        IP.A.records = (unsigned long long *)d_records.p;
-        for (size_t k = 0; k < ds.agg_idx.size(); k++) {
-            const int32_t a = ds.agg_idx[k];
-            IP.A.func[k] = aggs[a].func;
-            IP.A.val_off[k] = val_off[a];
-            IP.A.seen_off[k] = seen_off[a];
-            IP.A.input[k] = in;
-        }
+        /* every agg of the set reads ds.input_col, i.e. `in` */
+        fill_accum_params(IP.A, st, ds.agg_idx.data(),
+                          (int)ds.agg_idx.size());
         for (int attempt = 0;; attempt++) {
             IP.slots = (unsigned long long *)ds.d_slots.p;
             IP.mask = (uint32_t)(ds.n_slots - 1);
@@ -1628,7 +1604,8 @@ struct AggOp : gx_op {
         AggLocalParams LP;
         LP.A = AP;
         LP.groups = (int32_t)n_groups_host;
-        std::memcpy(LP.tmpl, tmpl, sizeof(tmpl));
+        std::memcpy(LP.tmpl, layout.tmpl, sizeof(LP.tmpl));
+        const int32_t stride = layout.desc.stride;
         /* as many replicas as the LDS budget holds, up to the maximum (Q1's
          * 22-u64 record x 4 groups: 16; 128 groups of it: 1) */
         int32_t rep = 1;
@@ -1832,21 +1809,9 @@ struct AggOp : gx_op {
             AP.base_krow = base_krow;
             AP.n = n;
             AP.global_group = (int)no_group_by;
-            AP.stride = stride;
-            AP.records = (unsigned long long *)d_records.p;
-            int32_t k = 0;
-            for (size_t a = 0; a < aggs.size(); a++) {
-                if (is_distinct[a]) continue; /* fed by the distinct pass */
-                AP.func[k] = aggs[a].func;
-                AP.val_off[k] = val_off[a];
-                AP.seen_off[k] = seen_off[a];
-                AP.dec_scale[k] = dec_scale[a];
-                if (aggs[a].input_col >= 0) AP.input[k] = st.views[aggs[a].input_col];
-                else std::memset(&AP.input[k], 0, sizeof(DevColView));
-                k++;
-            }
-            AP.n_aggs = k;
-            AP.dec_err = (uint32_t *)d_decerr.p;
+            /* the distinct aggs are fed by the distinct pass */
+            const int32_t k = (int32_t)plain_idx.size();
+            fill_accum_params(AP, st, plain_idx.data(), k);
             auto k_accum = has_dec ? k_agg_accumulate_dec : k_agg_accumulate;
             /* few groups: accumulate block-local in LDS. n_groups_host
              * covers this chunk's gids (assigned above), so every row fits */
@@ -1912,12 +1877,7 @@ struct AggOp : gx_op {
         const uint32_t ng = n_groups_host;
         std::vector<int32_t> otypes;
         for (int32_t gc : group_cols_) otypes.push_back(input_types[gc]);
-        for (auto &sp : aggs) {
-            bool f64 = sp.func == GX_AGG_SUM_F64 || sp.func == GX_AGG_MIN_F64 ||
-                       sp.func == GX_AGG_MAX_F64 || sp.func == GX_AGG_AVG_F64;
-            otypes.push_back(agg_func_is_dec(sp.func) ? GX_DECIMAL
-                             : f64 ? GX_F64 : GX_I64);
-        }
+        for (auto &sp : aggs) otypes.push_back(agg_func_result_type(sp.func));
         auto h = alloc_result_cols(otypes, ng, device, stream);
         if (!h) return -1;
         if (ng > 0) {
@@ -1955,21 +1915,17 @@ struct AggOp : gx_op {
                 col++;
             }
             EP.records = (const unsigned long long *)d_records.p;
-            EP.stride = stride;
             EP.n_groups = ng;
             EP.slot_of_gid = slot_records ? (const uint32_t *)d_slot_of_gid.p
                                           : nullptr;
-            EP.n_aggs = (int32_t)aggs.size();
+            EP.R = layout.desc;
             for (size_t a = 0; a < aggs.size(); a++) {
-                EP.func[a] = aggs[a].func;
-                EP.val_off[a] = val_off[a];
-                EP.seen_off[a] = seen_off[a];
                 EP.dec_scale[a] = dec_scale[a];
                 EP.out_vals[a] = h->bufs[col * 2].p;
                 EP.out_nulls[a] = (uint8_t *)h->bufs[col * 2 + 1].p;
                 col++;
             }
-            if (EP.n_aggs > 0 || EP.n_keys > 0)
+            if (EP.R.n_aggs > 0 || EP.n_keys > 0)
                 hipLaunchKernelGGL(k_agg_emit, dim3(gx_grid(ng)), dim3(256), 0,
                                    stream, EP);
             HIP_OK(hipStreamSynchronize(stream));

@@ -42,30 +42,6 @@ __global__ void k_fw_seg_reduce(AggAccumParams A, const uint32_t *seg,
         agg_apply(A, seg[i], i);
 }
 
-__global__ void k_fw_emit_whole(const unsigned long long *records,
-                                int32_t stride, int32_t val_off,
-                                int32_t seen_off, int32_t func,
-                                const uint32_t *seg, int64_t n,
-                                void *out_vals, uint8_t *out_nulls) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long *rec = records + (size_t)seg[i] * stride;
-        bool isnull = seen_off >= 0 && rec[seen_off] == 0ull;
-        out_nulls[i] = isnull;
-        bool f64 = func == GX_AGG_SUM_F64 || func == GX_AGG_MIN_F64 ||
-                   func == GX_AGG_MAX_F64 || func == GX_AGG_AVG_F64;
-        unsigned long long v = isnull ? 0ull : rec[val_off];
-        if (func == GX_AGG_AVG_F64)
-            ((double *)out_vals)[i] = isnull ? 0.0
-                : __builtin_bit_cast(double, v) / (double)rec[seen_off];
-        else if (f64)
-            ((double *)out_vals)[i] = isnull ? 0.0
-                : __builtin_bit_cast(double, v);
-        else
-            ((int64_t *)out_vals)[i] = (int64_t)v;
-    }
-}
-
 /* sliding MIN/MAX: sparse-table range queries. The ROWS frame span is
  * FIXED, so only floor(log2(span))+1 levels are built (level k holds the
  * op over [i, i+2^k-1], clamped to the array end); a query covers its
@@ -661,16 +637,15 @@ struct FWindowOp : gx_op {
         std::vector<int32_t> otypes = input_types;
         for (auto &f : frames) {
             switch (f.func) {
-            case GX_AGG_COUNT_ROW: case GX_AGG_COUNT_COL:
-            case GX_AGG_SUM_I64: case GX_AGG_SUM_I64N:
-            case GX_AGG_MIN_I64: case GX_AGG_MAX_I64:
-            case GX_AGG_BIT_AND: case GX_AGG_BIT_OR: case GX_AGG_BIT_XOR:
             case GX_AGG_NTILE:
                 otypes.push_back(GX_I64); break;
             case GX_AGG_FIRST_VALUE: case GX_AGG_LAST_VALUE:
             case GX_AGG_NTH_VALUE: case GX_AGG_LAG: case GX_AGG_LEAD:
                 otypes.push_back(input_types[f.input_col]); break;
-            default: otypes.push_back(GX_F64); break;
+            case GX_AGG_CUME_DIST: case GX_AGG_PERCENT_RANK:
+                otypes.push_back(GX_F64); break;
+            default:
+                otypes.push_back(agg_func_result_type(f.func)); break;
             }
         }
         auto h = alloc_result_cols(otypes, n, device, stream);
@@ -728,51 +703,27 @@ struct FWindowOp : gx_op {
                 continue;
             }
             if (f.kind == GX_FRAME_WHOLE_PARTITION) {
-                /* layout: one record per segment, val (+seen for
-                 * null-tracking funcs) */
-                bool tracks_null = !(f.func == GX_AGG_COUNT_ROW ||
-                                     f.func == GX_AGG_COUNT_COL ||
-                                     f.func == GX_AGG_SUM_I64 ||
-                                     f.func == GX_AGG_BIT_AND ||
-                                     f.func == GX_AGG_BIT_OR ||
-                                     f.func == GX_AGG_BIT_XOR);
-                int32_t stride = tracks_null ? 2 : 1;
-                unsigned long long tmpl0;
-                switch (f.func) {
-                case GX_AGG_MIN_I64: tmpl0 = (unsigned long long)INT64_MAX; break;
-                case GX_AGG_MAX_I64: tmpl0 = (unsigned long long)INT64_MIN; break;
-                case GX_AGG_MIN_F64: tmpl0 = __builtin_bit_cast(unsigned long long, (double)INFINITY); break;
-                case GX_AGG_MAX_F64: tmpl0 = __builtin_bit_cast(unsigned long long, (double)-INFINITY); break;
-                case GX_AGG_BIT_AND: tmpl0 = ~0ull; break;
-                default: tmpl0 = 0ull; break;
-                }
-                if (d_rec.grow((size_t)n_segs * stride * 8, stream)) return -1;
-                AggInitParams IP;
-                IP.records = (unsigned long long *)d_rec.p;
-                IP.stride = stride;
-                IP.from = 0;
-                IP.to = n_segs;
-                IP.tmpl[0] = tmpl0;
-                if (stride > 1) IP.tmpl[1] = 0ull;
-                hipLaunchKernelGGL(k_agg_init,
-                                   dim3(gx_grid((int64_t)n_segs * stride)),
-                                   dim3(256), 0, stream, IP);
+                /* one single-aggregate record per segment; the rows of a
+                 * segment all emit its record */
+                AggLayout L;
+                L.build(&f.func, 1);
+                const AggRecDesc &R = L.desc;
+                if (d_rec.grow((size_t)n_segs * R.stride * 8, stream))
+                    return -1;
+                agg_launch_init(L, d_rec.p, 0, n_segs, stream);
                 AggAccumParams A;
                 std::memset(&A, 0, sizeof(A));
-                A.n_aggs = 1;
-                A.stride = stride;
-                A.func[0] = f.func;
-                A.val_off[0] = 0;
-                A.seen_off[0] = tracks_null ? 1 : -1;
+                A.set_desc(R);
                 A.input[0] = in;
                 A.records = (unsigned long long *)d_rec.p;
                 hipLaunchKernelGGL(k_fw_seg_reduce, dim3(gx_grid(n)),
                                    dim3(256), 0, stream, A, seg, n);
-                hipLaunchKernelGGL(k_fw_emit_whole, dim3(gx_grid(n)),
+                hipLaunchKernelGGL(k_agg_emit_col, dim3(gx_grid(n)),
                                    dim3(256), 0, stream,
                                    (const unsigned long long *)d_rec.p,
-                                   stride, 0, tracks_null ? 1 : -1, f.func,
-                                   seg, n, h->bufs[col * 2].p,
+                                   R.stride, R.val_off[0], R.seen_off[0],
+                                   f.func, seg, (const uint32_t *)nullptr,
+                                   -1, 0, n, h->bufs[col * 2].p,
                                    (uint8_t *)h->bufs[col * 2 + 1].p);
             } else {
                 const bool is_range =

@@ -1,6 +1,7 @@
 /*
  * gxhip_groupjoin.inc — fused group-join (included by gxhip.hip after
- * gxhip_agg.inc: reuses agg_apply/k_agg_init record machinery and JoinOp's
+ * gxhip_agg.inc: per-position state records laid out by gx_agg_layout.h,
+ * accumulated by agg_apply and initialized by agg_launch_init, and JoinOp's
  * CSR build + pair-probe).
  *
  * Restates HashGroupJoinExec (operator/HashGroupJoinExec.java): one group
@@ -217,6 +218,15 @@ __global__ void k_gj_probe_inline(GJInlineProbeParams P) {
     gj_count_matches(P.matches, n_match);
 }
 
+/* matched = the position's used-bit, or where the op keeps none
+ * (count_off >= 0) a non-zero COUNT(*) word of its record */
+__device__ static inline bool gj_matched(const unsigned long long *rec,
+                                         const uint32_t *used,
+                                         int32_t count_off, uint32_t g) {
+    return count_off >= 0 ? rec[count_off] != 0ull
+                          : (used[g >> 5] >> (g & 31)) & 1u;
+}
+
 /* compact the matched positions (INNER emission list), with per-wave LDS
  * staging so the global counter sees 1 atomic per 512 hits. Matched = the
  * used-bit, or where the op keeps none (count_off >= 0) a non-zero
@@ -248,9 +258,8 @@ __global__ void k_gj_compact(const uint32_t *used,
         if (!__ballot(active)) break;
         bool want = false;
         if (active)
-            want = count_off >= 0
-                ? records[(size_t)i * rec_stride + count_off] != 0ull
-                : (used[i >> 5] >> (i & 31)) & 1u;
+            want = gj_matched(records + (size_t)i * rec_stride, used,
+                              count_off, (uint32_t)i);
         unsigned long long m = __ballot(want);
         uint32_t add = (uint32_t)__popcll(m);
         if (cnt + add > GX_EMIT_STAGE) flush();
@@ -262,62 +271,49 @@ __global__ void k_gj_compact(const uint32_t *used,
     flush();
 }
 
-/* emit one agg value column for the listed groups. idx==NULL emits groups
- * 0..n-1 in order (LEFT). count_row_null_row: add 1 to COUNT(*) of
- * unmatched groups (buildNullRow's null-row accumulation). */
-__global__ void k_gj_emit(const unsigned long long *records, int32_t stride,
-                          int32_t val_off, int32_t seen_off, int32_t func,
-                          const uint32_t *idx, const uint32_t *used,
-                          int32_t count_off, int count_row_null_row,
-                          int64_t n,
-                          void *out_vals, uint8_t *out_nulls) {
+/* emit one agg value column (8-B values: I64 results and F64 bit patterns
+ * alike) for the listed records: output row i reads record idx[i], or
+ * record i where idx == NULL (LEFT). count_row_null_row: add 1 to COUNT(*)
+ * of unmatched groups (buildNullRow's null-row accumulation); `used` and
+ * count_off are read only then. */
+__global__ void k_agg_emit_col(const unsigned long long *records,
+                               int32_t stride, int32_t val_off,
+                               int32_t seen_off, int32_t func,
+                               const uint32_t *idx, const uint32_t *used,
+                               int32_t count_off, int count_row_null_row,
+                               int64_t n, void *out_vals,
+                               uint8_t *out_nulls) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         uint32_t g = idx ? idx[i] : (uint32_t)i;
         const unsigned long long *rec = records + (size_t)g * stride;
-        bool matched = count_off >= 0 ? rec[count_off] != 0ull
-                                      : (used[g >> 5] >> (g & 31)) & 1u;
-        bool isnull = seen_off >= 0 && rec[seen_off] == 0ull;
-        out_nulls[i] = isnull;
-        bool f64 = func == GX_AGG_SUM_F64 || func == GX_AGG_MIN_F64 ||
-                   func == GX_AGG_MAX_F64 || func == GX_AGG_AVG_F64;
-        unsigned long long v = isnull ? 0ull : rec[val_off];
-        if (func == GX_AGG_AVG_F64) {
-            ((double *)out_vals)[i] = isnull ? 0.0
-                : __builtin_bit_cast(double, v) / (double)rec[seen_off];
-        } else if (f64) {
-            ((double *)out_vals)[i] = isnull ? 0.0
-                : __builtin_bit_cast(double, v);
-        } else {
-            int64_t x = (int64_t)v;
-            if (func == GX_AGG_COUNT_ROW && !matched && count_row_null_row)
-                x += 1;
-            ((int64_t *)out_vals)[i] = x;
-        }
+        AggDecoded d = agg_decode(func, rec, val_off, seen_off);
+        out_nulls[i] = d.isnull;
+        if (count_row_null_row && func == GX_AGG_COUNT_ROW &&
+            !gj_matched(rec, used, count_off, g))
+            d.bits += 1;
+        ((unsigned long long *)out_vals)[i] = d.bits;
     }
 }
 
 /* One-kernel emission for fixed-width group columns: per emitted position
  * the record (one random line) is read once and every key and aggregate
- * column written from it. Same values as k_gather + k_gj_emit; an output
+ * column written from it. Same values as k_gather + k_agg_emit_col; an output
  * whose nulls pointer is NULL (null-free source column, aggregate without
  * a seen slot) skips the null store. */
 struct GJEmitParams {
     const unsigned long long *records;
-    int32_t stride;
+    AggRecDesc R;
     const uint32_t *idx;            /* NULL = positions 0..n-1 (LEFT) */
     const uint32_t *used;
     int32_t count_off;              /* >= 0: matched = that word != 0 */
     int count_row_null_row;
     int64_t n;
-    int32_t n_keys, n_aggs;
+    int32_t n_keys;
     DevColView key_src[GX_MAX_COLS];
     int32_t key_words[GX_MAX_COLS]; /* element size in 4-B words */
     void *key_vals[GX_MAX_COLS];
     uint8_t *key_nulls[GX_MAX_COLS];
-    int32_t func[GX_MAX_COLS];
-    int32_t val_off[GX_MAX_COLS];
-    int32_t seen_off[GX_MAX_COLS];
     void *agg_vals[GX_MAX_COLS];
     uint8_t *agg_nulls[GX_MAX_COLS];
 };
@@ -335,26 +331,17 @@ __global__ void k_gj_emit_all(GJEmitParams P) {
             uint32_t *dv = (uint32_t *)P.key_vals[k] + (size_t)i * w;
             for (int32_t j = 0; j < w; j++) dv[j] = nn ? 0u : sv[j];
         }
-        const unsigned long long *rec = P.records + (size_t)g * P.stride;
-        const bool matched = P.count_off >= 0
-            ? rec[P.count_off] != 0ull
-            : (P.used[g >> 5] >> (g & 31)) & 1u;
-        for (int a = 0; a < P.n_aggs; a++) {
-            const int32_t func = P.func[a], so = P.seen_off[a];
-            const unsigned long long seen = so >= 0 ? rec[so] : 1ull;
-            const bool isnull = seen == 0ull;
-            if (P.agg_nulls[a]) P.agg_nulls[a][i] = isnull;
-            const unsigned long long v = isnull ? 0ull : rec[P.val_off[a]];
-            if (func == GX_AGG_AVG_F64) {
-                ((double *)P.agg_vals[a])[i] = isnull ? 0.0
-                    : __builtin_bit_cast(double, v) / (double)seen;
-            } else if (func == GX_AGG_COUNT_ROW) {
-                ((int64_t *)P.agg_vals[a])[i] = (int64_t)v +
-                    ((!matched && P.count_row_null_row) ? 1 : 0);
-            } else {
-                /* I64 results and F64 bit patterns alike */
-                ((unsigned long long *)P.agg_vals[a])[i] = v;
-            }
+        const unsigned long long *rec = P.records + (size_t)g * P.R.stride;
+        const bool matched = gj_matched(rec, P.used, P.count_off, g);
+        for (int a = 0; a < P.R.n_aggs; a++) {
+            const int32_t func = P.R.func[a];
+            AggDecoded d = agg_decode(func, rec, P.R.val_off[a],
+                                      P.R.seen_off[a]);
+            if (P.agg_nulls[a]) P.agg_nulls[a][i] = d.isnull;
+            if (func == GX_AGG_COUNT_ROW && !matched && P.count_row_null_row)
+                d.bits += 1;
+            /* I64 results and F64 bit patterns alike */
+            ((unsigned long long *)P.agg_vals[a])[i] = d.bits;
         }
     }
 }
@@ -374,10 +361,7 @@ struct GroupJoinOp : gx_op {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double kernel_ms = 0.0;
     int64_t rows_total = 0, probe_launches = 0, matches_total = 0;
-    int32_t stride = 0;
-    int32_t val_off[GX_MAX_COLS] = {0};
-    int32_t seen_off[GX_MAX_COLS] = {0};
-    unsigned long long tmpl[2 * GX_MAX_COLS] = {0};
+    AggLayout layout;        /* the per-position state record, over aggs[] */
     bool built = false, emitted = false;
     bool wide_ok = false;    /* cfg allows wide mode */
     bool wide = false;       /* chosen at do_build (needs null-free keys) */
@@ -427,34 +411,7 @@ struct GroupJoinOp : gx_op {
         jop.reset(new JoinOp(&jc));
         jop->null_safe_keys = true;
 
-        /* AoS record layout (same scheme as AggOp) */
-        int32_t off = 0;
-        for (size_t a = 0; a < aggs.size(); a++) {
-            val_off[a] = off;
-            switch (aggs[a].func) {
-            case GX_AGG_MIN_I64: tmpl[off] = (unsigned long long)INT64_MAX; break;
-            case GX_AGG_MAX_I64: tmpl[off] = (unsigned long long)INT64_MIN; break;
-            case GX_AGG_MIN_F64: tmpl[off] = __builtin_bit_cast(unsigned long long, (double)INFINITY); break;
-            case GX_AGG_MAX_F64: tmpl[off] = __builtin_bit_cast(unsigned long long, (double)-INFINITY); break;
-            case GX_AGG_BIT_AND: tmpl[off] = ~0ull; break;
-            default: tmpl[off] = 0ull; break;
-            }
-            off++;
-            bool tracks_null = !(aggs[a].func == GX_AGG_COUNT_ROW ||
-                                 aggs[a].func == GX_AGG_COUNT_COL ||
-                                 aggs[a].func == GX_AGG_SUM_I64 ||
-                                 aggs[a].func == GX_AGG_BIT_AND ||
-                                 aggs[a].func == GX_AGG_BIT_OR ||
-                                 aggs[a].func == GX_AGG_BIT_XOR);
-            if (tracks_null) {
-                seen_off[a] = off;
-                tmpl[off] = 0ull;
-                off++;
-            } else {
-                seen_off[a] = -1;
-            }
-        }
-        stride = off > 0 ? off : 1;
+        layout = agg_layout_of(aggs);
         wide_ok = keys.size() == 1 && keys[0].unified_type == GX_I64 &&
                   aggs.size() <= 2;
         for (auto &a : aggs)
@@ -492,21 +449,16 @@ struct GroupJoinOp : gx_op {
         count_off = -1;
         if (inline_tab && cfg.join_type == GX_JOIN_INNER)
             for (size_t a = 0; a < aggs.size() && count_off < 0; a++)
-                if (aggs[a].func == GX_AGG_COUNT_ROW) count_off = val_off[a];
+                if (aggs[a].func == GX_AGG_COUNT_ROW)
+                    count_off = layout.desc.val_off[a];
         if (jop->do_build_with(launch_insert)) return -1;
         const int64_t n = jop->build.n_rows;
         if (d_meta.grow(16, stream)) return -1;
         HIP_OK(hipMemsetAsync(d_meta.p, 0, 16, stream));
+        const AggRecDesc &R = layout.desc;
         if (n > 0) {
-            if (d_records.grow((size_t)n * stride * 8, stream)) return -1;
-            AggInitParams P;
-            P.records = (unsigned long long *)d_records.p;
-            P.stride = stride;
-            P.from = 0;
-            P.to = n;
-            std::memcpy(P.tmpl, tmpl, sizeof(tmpl));
-            hipLaunchKernelGGL(k_agg_init, dim3(gx_grid(n * stride)),
-                               dim3(256), 0, stream, P);
+            if (d_records.grow((size_t)n * R.stride * 8, stream)) return -1;
+            agg_launch_init(layout, d_records.p, 0, n, stream);
         }
         size_t words = (size_t)((n + 31) / 32);
         if (words == 0) words = 1;
@@ -520,8 +472,10 @@ struct GroupJoinOp : gx_op {
             hipLaunchKernelGGL(k_gjw_expand, dim3(gx_grid(n)), dim3(256), 0,
                                stream, (const JoinEntry *)jop->d_entries.p, n,
                                jop->build.view(jop->build_key_cols[0]),
-                               (GJWideEntry *)d_wide.p, tmpl[val_off[0]],
-                               aggs.size() > 1 ? tmpl[val_off[1]] : 0ull);
+                               (GJWideEntry *)d_wide.p,
+                               layout.tmpl[R.val_off[0]],
+                               aggs.size() > 1 ? layout.tmpl[R.val_off[1]]
+                                               : 0ull);
         }
         built = true;
         return 0;
@@ -607,15 +561,8 @@ struct GroupJoinOp : gx_op {
 
     /* the aggregate half of a plain probe's params (zeroed by the caller) */
     void fill_accum(AggAccumParams &A, const StagedChunk &st) const {
-        A.n_aggs = (int32_t)aggs.size();
-        A.stride = stride;
-        for (size_t a = 0; a < aggs.size(); a++) {
-            A.func[a] = aggs[a].func;
-            A.val_off[a] = val_off[a];
-            A.seen_off[a] = seen_off[a];
-            if (aggs[a].input_col >= 0)
-                A.input[a] = st.views[aggs[a].input_col];
-        }
+        A.set_desc(layout.desc);
+        agg_bind_inputs(A.input, aggs.data(), nullptr, A.n_aggs, st.views);
         A.records = (unsigned long long *)d_records.p;
     }
 
@@ -644,12 +591,13 @@ struct GroupJoinOp : gx_op {
         emitted = true;
         const int64_t n_build = jop->build.n_rows;
         if (n_build == 0) return 0;
+        const AggRecDesc &R = layout.desc;
         if (wide) {
             hipLaunchKernelGGL(k_gjw_unpack, dim3(gx_grid(n_build)), dim3(256),
                                0, stream, (const GJWideEntry *)d_wide.p,
                                n_build, (unsigned long long *)d_records.p,
-                               stride, val_off[0],
-                               aggs.size() > 1 ? val_off[1] : 0,
+                               R.stride, R.val_off[0],
+                               aggs.size() > 1 ? R.val_off[1] : 0,
                                (int32_t)aggs.size(), (uint32_t *)d_used.p);
         }
 
@@ -663,7 +611,7 @@ struct GroupJoinOp : gx_op {
             hipLaunchKernelGGL(k_gj_compact, dim3(gx_grid(n_build)), dim3(256),
                                0, stream, (const uint32_t *)d_used.p,
                                (const unsigned long long *)d_records.p,
-                               stride, count_off, n_build,
+                               R.stride, count_off, n_build,
                                (uint32_t *)d_gidx.p, (uint32_t *)d_cnt.p);
             uint32_t cnt = 0;
             HIP_OK(hipMemcpyAsync(&cnt, d_cnt.p, 4, hipMemcpyDeviceToHost,
@@ -676,16 +624,7 @@ struct GroupJoinOp : gx_op {
 
         std::vector<int32_t> otypes;
         for (int32_t gc : group_cols_) otypes.push_back(build_types[gc]);
-        for (auto &sp : aggs) {
-            switch (sp.func) {
-            case GX_AGG_COUNT_ROW: case GX_AGG_COUNT_COL:
-            case GX_AGG_SUM_I64: case GX_AGG_SUM_I64N:
-            case GX_AGG_MIN_I64: case GX_AGG_MAX_I64:
-            case GX_AGG_BIT_AND: case GX_AGG_BIT_OR: case GX_AGG_BIT_XOR:
-                otypes.push_back(GX_I64); break;
-            default: otypes.push_back(GX_F64); break;
-            }
-        }
+        for (auto &sp : aggs) otypes.push_back(agg_func_result_type(sp.func));
         bool fixed_width = group_cols_.size() <= GX_MAX_COLS;
         for (int32_t gc : group_cols_)
             if (build_types[gc] == GX_SLICE) fixed_width = false;
@@ -696,21 +635,20 @@ struct GroupJoinOp : gx_op {
             for (int32_t gc : group_cols_)
                 null_free.push_back(!jop->build.view(gc).has_nulls);
             for (size_t a = 0; a < aggs.size(); a++)
-                null_free.push_back(seen_off[a] < 0);
+                null_free.push_back(R.seen_off[a] < 0);
             auto h = alloc_result_cols(otypes, n_emit, device, stream,
                                        &null_free);
             if (!h) return -1;
             GJEmitParams E;
             std::memset(&E, 0, sizeof(E));
             E.records = (const unsigned long long *)d_records.p;
-            E.stride = stride;
+            E.R = R;
             E.idx = idx;
             E.used = (const uint32_t *)d_used.p;
             E.count_off = count_off;
             E.count_row_null_row = (int)emit_all;
             E.n = n_emit;
             E.n_keys = (int32_t)group_cols_.size();
-            E.n_aggs = (int32_t)aggs.size();
             size_t col = 0;
             for (size_t k = 0; k < group_cols_.size(); k++, col++) {
                 E.key_src[k] = jop->build.view(group_cols_[k]);
@@ -720,9 +658,6 @@ struct GroupJoinOp : gx_op {
                 E.key_nulls[k] = (uint8_t *)h->bufs[col * 2 + 1].p;
             }
             for (size_t a = 0; a < aggs.size(); a++, col++) {
-                E.func[a] = aggs[a].func;
-                E.val_off[a] = val_off[a];
-                E.seen_off[a] = seen_off[a];
                 E.agg_vals[a] = h->bufs[col * 2].p;
                 E.agg_nulls[a] = (uint8_t *)h->bufs[col * 2 + 1].p;
             }
@@ -758,9 +693,11 @@ struct GroupJoinOp : gx_op {
             col++;
         }
         for (size_t a = 0; a < aggs.size(); a++) {
-            hipLaunchKernelGGL(k_gj_emit, dim3(gx_grid(n_emit)), dim3(256), 0,
-                               stream, (const unsigned long long *)d_records.p,
-                               stride, val_off[a], seen_off[a], aggs[a].func,
+            hipLaunchKernelGGL(k_agg_emit_col, dim3(gx_grid(n_emit)),
+                               dim3(256), 0, stream,
+                               (const unsigned long long *)d_records.p,
+                               R.stride, R.val_off[a], R.seen_off[a],
+                               R.func[a],
                                emit_all ? nullptr : idx,
                                (const uint32_t *)d_used.p, count_off,
                                (int)emit_all,

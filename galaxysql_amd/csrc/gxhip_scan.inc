@@ -508,11 +508,7 @@ k_probe_scan(ProbeParams P, ScanPreds S, uint32_t *kept) {
  * segment next to ProbeParams and ScanPreds (together past 4 KB), so they
  * travel in a small device buffer read through wave-uniform loads. */
 struct GJAccum {
-    int32_t n_aggs;
-    int32_t stride;                 /* record size in u64s */
-    int32_t func[GX_MAX_COLS];
-    int32_t val_off[GX_MAX_COLS];
-    int32_t seen_off[GX_MAX_COLS];
+    AggRecDesc R;                   /* first: the buffer's leading bytes */
     int32_t op[GX_MAX_COLS];        /* the input's projection (unused for
                                        COUNT(*)) */
     DevColView a[GX_MAX_COLS];
@@ -553,20 +549,20 @@ struct AccumFlush {
                 agg_slot_ops_clear(o);
 #pragma unroll
                 for (int a = 0; a < GX_AGG_T_SLOTS; a++) {
-                    if (a >= G.n_aggs || !active) continue;
+                    if (a >= G.R.n_aggs || !active) continue;
                     AggVal v;
                     v.bits = 0;
                     v.hi = 0;
                     v.type = GX_I64;
                     v.isnull = false;
-                    if (G.func[a] != GX_AGG_COUNT_ROW)
+                    if (G.R.func[a] != GX_AGG_COUNT_ROW)
                         v = proj_value(G.op[a], G.a[a], G.b[a], G.c[a],
                                        G.d[a], row);
-                    agg_slot_ops_put(o, G.func[a], G.val_off[a],
-                                     G.seen_off[a], v);
+                    agg_slot_ops_put(o, G.R.func[a], G.R.val_off[a],
+                                     G.R.seen_off[a], v);
                 }
                 if ((seen_w & w) == 0) atomicOr(&G.used[pos >> 5], w);
-                agg_add_transposed(G.records, G.stride, G.t_width, G.t_f64,
+                agg_add_transposed(G.records, G.R.stride, G.t_width, G.t_f64,
                                    pos, o, E.lane);
             }
             if (E.lane == 0) atomicAdd(G.matches, (unsigned long long)E.cnt);
@@ -580,17 +576,18 @@ struct AccumFlush {
             /* test-then-set: one RMW */
             if (G.used && (G.used[pos >> 5] & w) == 0)
                 atomicOr(&G.used[pos >> 5], w);
-            unsigned long long *rec = G.records + (size_t)pos * G.stride;
-            for (int a = 0; a < G.n_aggs; a++) {
+            unsigned long long *rec = G.records + (size_t)pos * G.R.stride;
+            for (int a = 0; a < G.R.n_aggs; a++) {
                 AggVal v;
                 v.bits = 0;
                 v.hi = 0;
                 v.type = GX_I64;
                 v.isnull = false;
-                if (G.func[a] != GX_AGG_COUNT_ROW)
+                if (G.R.func[a] != GX_AGG_COUNT_ROW)
                     v = proj_value(G.op[a], G.a[a], G.b[a], G.c[a], G.d[a],
                                    row);
-                agg_rmw(G.func[a], rec, G.val_off[a], G.seen_off[a], v);
+                agg_rmw(G.R.func[a], rec, G.R.val_off[a], G.R.seen_off[a],
+                        v);
             }
         }
         if (E.lane == 0) atomicAdd(G.matches, (unsigned long long)E.cnt);
@@ -1145,12 +1142,8 @@ int gj_probe_scan_fused(GroupJoinOp *g, ScanOp *s, const gx_chunk *raw,
 
     GJAccum A;
     std::memset(&A, 0, sizeof(A));
-    A.n_aggs = (int32_t)g->aggs.size();
-    A.stride = g->stride;
+    A.R = g->layout.desc;
     for (size_t a = 0; a < g->aggs.size(); a++) {
-        A.func[a] = g->aggs[a].func;
-        A.val_off[a] = g->val_off[a];
-        A.seen_off[a] = g->seen_off[a];
         if (g->aggs[a].input_col < 0) continue;
         const gx_proj &pr = s->projs[(size_t)g->aggs[a].input_col];
         A.op[a] = pr.op;
@@ -1161,14 +1154,14 @@ int gj_probe_scan_fused(GroupJoinOp *g, ScanOp *s, const gx_chunk *raw,
             A.d[a] = st.views[pr.d];
         }
     }
-    bool additive = g->stride <= GX_AGG_T_SLOTS;
+    bool additive = A.R.stride <= GX_AGG_T_SLOTS;
     for (size_t a = 0; a < g->aggs.size(); a++)
         additive = additive && agg_func_additive(g->aggs[a].func);
     if (additive) {
-        A.t_width = g->stride <= 1 ? 1 : g->stride == 2 ? 2 : 4;
+        A.t_width = A.R.stride <= 1 ? 1 : A.R.stride == 2 ? 2 : 4;
         for (size_t a = 0; a < g->aggs.size(); a++)
             if (agg_func_adds_f64(g->aggs[a].func))
-                A.t_f64 |= 1u << g->val_off[a];
+                A.t_f64 |= 1u << A.R.val_off[a];
     }
     A.records = (unsigned long long *)g->d_records.p;
     A.used = g->count_off >= 0 ? nullptr : (uint32_t *)g->d_used.p;

@@ -393,13 +393,10 @@ struct WindowOp : gx_op {
         std::vector<int32_t> otypes = input_types;
         for (auto &sp : aggs) {
             switch (sp.func) {
-            case GX_AGG_COUNT_ROW: case GX_AGG_COUNT_COL:
-            case GX_AGG_SUM_I64: case GX_AGG_SUM_I64N:
-            case GX_AGG_MIN_I64: case GX_AGG_MAX_I64:
-            case GX_AGG_BIT_AND: case GX_AGG_BIT_OR: case GX_AGG_BIT_XOR:
             case GX_AGG_RANK: case GX_AGG_DENSE_RANK:
                 otypes.push_back(GX_I64); break;
-            default: otypes.push_back(GX_F64); break;
+            default:
+                otypes.push_back(agg_func_result_type(sp.func)); break;
             }
         }
         if (n == 0) {
