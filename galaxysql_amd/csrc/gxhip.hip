@@ -343,10 +343,16 @@ __global__ void k_join_scatter(const int32_t *hashes, const uint8_t *keynull,
 /* ---- bloom pre-filter (fast path) --------------------------------------
  * The reference tests a FastIntBloomFilter before the bucket walk
  * (AbstractHashJoinExec.java:80-106, FastIntBloomFilter.java:30-61).
- * Here: a cache-line-BLOCKED bloom — one 64-B line per key, two bits
- * inside it — sized ~8 bits/build key so it stays Infinity-Cache-resident
- * while the inline-bucket table does not: a negative probe then costs an
- * L3 hit instead of a random HBM line. Bit placement is internal (the
+ * Here: a cache-line-BLOCKED bloom — one 64-B line per key, k bits
+ * inside it. A negative probe then costs one filter line instead of a
+ * random table line. Either is one fabric request (random lines cost the
+ * same from the Infinity Cache as from HBM), so what the filter saves is
+ * requests: the bucket line of a negative that passes, and the filter
+ * line itself where the XCD's L2 holds it. Measured (profiles/README.md
+ * Round 9), the 8-9 bits/key filter of a 14.6M-key build (16 MiB) finds
+ * at most 15 % of its words in L2; at half the size with three bits the
+ * step is faster, at a quarter the false positives cost more than L2
+ * returns: bloom_geometry below. Bit placement is internal (the
  * filter only gates the bucket read; false positives fall through), so
  * it uses a 64-bit mix of the key rather than the Java rotate chain. */
 __device__ static inline uint64_t bloom_mix(int64_t key) {
@@ -355,22 +361,51 @@ __device__ static inline uint64_t bloom_mix(int64_t key) {
     return x;
 }
 
-/* Both bits of a key sit in ONE 64-bit word of its 64-B line, so the build
- * sets them with a single 64-bit atomicOr (random atomics are paid per
- * request, not per byte) and the probe tests them with one 8-B load.
- * line_mask = (n_lines - 1); lines of 8 u64 words. */
-__device__ static inline uint64_t bloom_bits(uint64_t x) {
-    return (1ull << ((x >> 35) & 63u)) | (1ull << ((x >> 41) & 63u));
+/* All k bits of a key (k = 1..3, chosen per build: bloom_geometry) sit in
+ * ONE 64-bit word of its 64-B line, so the build sets them with a single
+ * 64-bit atomicOr (random atomics are paid per request, not per byte) and
+ * the probe tests them with one 8-B load. The build (join_insert_row) and
+ * every probe (bloom_test, probe_scan_body) take word and bits from this
+ * one pair of helpers with the op's (line_mask, k), so they cannot
+ * disagree. k is wave-uniform; the selects keep bloom_bits branch-free.
+ * line_mask = (n_lines - 1), 0 for a one-line filter; lines of 8 u64
+ * words. Fields of x: line 0..31, word 32..34, bits 35..40 / 41..46 /
+ * 47..52. */
+__device__ static inline uint64_t bloom_bits(uint64_t x, uint32_t k) {
+    uint64_t bits = 1ull << ((x >> 35) & 63u);
+    bits |= k >= 2 ? 1ull << ((x >> 41) & 63u) : 0ull;
+    bits |= k >= 3 ? 1ull << ((x >> 47) & 63u) : 0ull;
+    return bits;
 }
 __device__ static inline size_t bloom_word(uint64_t x, uint32_t line_mask) {
     return (size_t)((uint32_t)x & line_mask) * 8 + ((uint32_t)(x >> 32) & 7u);
 }
 
 __device__ static inline bool bloom_test(const uint32_t *bloom,
-                                         uint32_t line_mask, int64_t key) {
+                                         uint32_t line_mask, uint32_t k,
+                                         int64_t key) {
     uint64_t x = bloom_mix(key);
-    uint64_t bits = bloom_bits(x);
+    uint64_t bits = bloom_bits(x, k);
     return (((const uint64_t *)bloom)[bloom_word(x, line_mask)] & bits) == bits;
+}
+
+/* The filter's geometry for an n-row build: n_lines = pow2(n / 64) >> shift
+ * (at least one line) and k bits per key. A probe's filter word is one
+ * fabric request unless the XCD's 4-MiB L2 holds its line. L2 holds at most
+ * 4 MiB / T of a T-byte filter read uniformly, and the probe's stream and
+ * the lines of its matches leave the filter about 0.6 of that (measured:
+ * 15 % hits at T = 16 MiB), so a filter past 0.6 x L2 is halved and pays
+ * for its denser words with a third bit (profiles/README.md Round 9 has
+ * the sweep). */
+#define GX_L2_BYTES (INT64_C(4) << 20)
+static inline void bloom_geometry(int64_t n, int &shift, uint32_t &k) {
+    const int64_t bytes = gx_pow2(std::max<int64_t>(n / 64, 1)) * 64;
+    shift = 0;
+    k = 2;
+    if (bytes * 5 > GX_L2_BYTES * 3) { /* bytes > 0.6 x L2 */
+        shift = 1;
+        k = 3;
+    }
 }
 
 /* ---- inline-bucket build (plain joins) --------------------------------
@@ -400,6 +435,7 @@ struct JoinInsertParams {
     uint32_t *spill_count;
     unsigned long long *bloom; /* NULL = no bloom */
     uint32_t bloom_mask;
+    uint32_t bloom_k;         /* bits per key, 1..3 */
 };
 
 /* bucket + entry key of build row i (the entry key is the I64 key itself on
@@ -437,7 +473,7 @@ __device__ static inline void join_insert_row(const JoinInsertParams &P,
         if (P.bloom) {
             uint64_t x = bloom_mix(key);
             atomicOr(&P.bloom[bloom_word(x, P.bloom_mask)],
-                     (unsigned long long)bloom_bits(x));
+                     (unsigned long long)bloom_bits(x, P.bloom_k));
         }
     }
     /* wave-aggregated append: one counter atomic per wave (a per-lane
@@ -660,6 +696,7 @@ struct ProbeParams {
     JoinCondDev conds[GX_MAX_CONDS];
     const uint32_t *bloom;      /* blocked bloom pre-filter; NULL = off */
     uint32_t bloom_mask;
+    uint32_t bloom_k;           /* bits per key, as built */
 };
 
 __device__ static inline bool join_conds_pass(const ProbeParams &P,
@@ -822,7 +859,8 @@ __device__ static inline void probe_one(const ProbeParams &P, EmitStage &E,
         i = r.rowid & 0x7FFFFFFFu;
         if (active && !(r.rowid & 0x80000000u)) {
             want_key = r.key;
-            if (!P.bloom || bloom_test(P.bloom, P.bloom_mask, want_key)) {
+            if (!P.bloom ||
+                bloom_test(P.bloom, P.bloom_mask, P.bloom_k, want_key)) {
                 uint32_t b = (uint32_t)gx_mix(r.hash) & P.mask;
                 ebase = (uint64_t)b * 4;
                 e0 = P.table[ebase];
@@ -834,7 +872,8 @@ __device__ static inline void probe_one(const ProbeParams &P, EmitStage &E,
         const DevColView &kc = P.probe_keys.col[0];
         if (active && !col_is_null(kc, i)) {
             want_key = ((const int64_t *)kc.values)[i];
-            if (!P.bloom || bloom_test(P.bloom, P.bloom_mask, want_key)) {
+            if (!P.bloom ||
+                bloom_test(P.bloom, P.bloom_mask, P.bloom_k, want_key)) {
                 uint32_t b = (uint32_t)gx_mix(gx_hash_i64(want_key)) & P.mask;
                 ebase = (uint64_t)b * 4;
                 e0 = P.table[ebase];
@@ -1336,6 +1375,7 @@ struct JoinOp : gx_op {
     bool probe_buf_init = false;
     DevStore build;          /* build-side columns in HBM */
     uint32_t bloom_mask = 0;
+    uint32_t bloom_k = 2;
     uint32_t mask = 0;
     int64_t n_buckets = 0;
     bool fast_i64 = false;
@@ -1546,15 +1586,26 @@ struct JoinOp : gx_op {
             }
             /* bloom pre-filter: GX_BLOOM=1 forces on, =0 off; default
              * on for builds whose table exceeds the Infinity Cache
-             * while the bloom (8 bits/key) still fits (the regime
-             * where a negative saves a random HBM line) */
+             * while the bloom (4-9 bits/key, bloom_geometry) still
+             * fits (the regime where a negative saves a random HBM
+             * line) */
             const char *be = getenv("GX_BLOOM");
             bool use_bloom = fast_i64 &&
                 (be ? be[0] == '1'
                     : (cfg.enable_bloom == 1 && n >= (1 << 16) &&
                        n <= INT64_C(200) << 20));
             if (use_bloom) {
-                int64_t n_lines = gx_pow2(std::max<int64_t>(n / 64, 1));
+                int shift = 0;
+                bloom_geometry(n, shift, bloom_k);
+                /* GX_BLOOM_SHIFT (0..3) / GX_BLOOM_K (1..3) override it */
+                if (const char *se = getenv("GX_BLOOM_SHIFT"))
+                    if (se[0] >= '0' && se[0] <= '3' && !se[1])
+                        shift = se[0] - '0';
+                if (const char *ke = getenv("GX_BLOOM_K"))
+                    if (ke[0] >= '1' && ke[0] <= '3' && !ke[1])
+                        bloom_k = (uint32_t)(ke[0] - '0');
+                int64_t n_lines = std::max<int64_t>(
+                    gx_pow2(std::max<int64_t>(n / 64, 1)) >> shift, 1);
                 bloom_mask = (uint32_t)(n_lines - 1);
                 if (d_bloom.grow((size_t)n_lines * 64, stream)) return -1;
                 HIP_OK(hipMemsetAsync(d_bloom.p, 0, (size_t)n_lines * 64,
@@ -1572,6 +1623,7 @@ struct JoinOp : gx_op {
             IP.spill_count = (uint32_t *)d_counts.p;
             IP.bloom = use_bloom ? (unsigned long long *)d_bloom.p : nullptr;
             IP.bloom_mask = bloom_mask;
+            IP.bloom_k = bloom_k;
             launch_insert(IP);
             uint32_t n_spill = 0;
             HIP_OK(hipMemcpyAsync(&n_spill, d_counts.p, 4,
@@ -1850,6 +1902,7 @@ struct JoinOp : gx_op {
             P.n_parts = 0;
             P.bloom = (const uint32_t *)d_bloom.p;
             P.bloom_mask = bloom_mask;
+            P.bloom_k = bloom_k;
             P.fast_i64 = (int)fast_i64;
             P.build_keys = key_views(build, build_key_cols);
             P.probe_keys = pk;

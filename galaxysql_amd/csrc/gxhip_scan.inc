@@ -449,7 +449,7 @@ __device__ static inline void probe_scan_body(const ProbeParams &P,
 #pragma unroll
             for (int r = 0; r < GX_PS_R; r++) {
                 const uint64_t x = bloom_mix(key[r]);
-                bits[r] = bloom_bits(x);
+                bits[r] = bloom_bits(x, P.bloom_k);
                 word[r] = ((live >> r) & 1u)
                     ? bloom[bloom_word(x, P.bloom_mask)] : 0ull;
             }
@@ -954,6 +954,7 @@ int probe_scan_pairs(JoinOp *j, ScanOp *s, const StagedChunk &st,
         P.n_probe = n;
         P.bloom = (const uint32_t *)j->d_bloom.p;
         P.bloom_mask = j->bloom_mask;
+        P.bloom_k = j->bloom_k;
         P.fast_i64 = 1;
         P.build_keys = j->key_views(j->build, j->build_key_cols);
         P.probe_keys.n = 1;
@@ -1133,6 +1134,7 @@ int gj_probe_scan_fused(GroupJoinOp *g, ScanOp *s, const gx_chunk *raw,
     P.n_probe = n;
     P.bloom = (const uint32_t *)j->d_bloom.p;
     P.bloom_mask = j->bloom_mask;
+    P.bloom_k = j->bloom_k;
     P.fast_i64 = 1;
     P.probe_keys.n = 1;
     P.probe_keys.col[0] = st.views[kp.a];
